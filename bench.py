@@ -2,7 +2,10 @@
 """Headline benchmark: whole-node output tokens/s (+ p50 per-token latency) of Llama-2-7B
 layer-sharded over N MI355X GPUs (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    (a plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON
+     line; --full adds the side measurements: batch-1 / mid-batch latency passes, the TTFT probe,
+     the other models)
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
              --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
@@ -61,18 +64,26 @@ def parse():
     ap.add_argument("--trace", default="", help="write per-rank Chrome-trace timelines of the timed steps here")
     ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="fp8: OCP e4m3 projection/lm_head weights with per-row scales (W8A16, not the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline (and --dump-outputs), also run the side measurements: the batch-1 "
+                         "and mid-batch latency passes, the TTFT probe and the other models (--latency-steps, "
+                         "--mid-batch, --ttft-lens, --extras). Off: their keys in the JSON line are null / absent")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step left with the caller (token ids, "
+                         "final hidden state; the ids of micro-batch 0 over the whole run) as DIR/<name>.npy, "
+                         "float32 / float64, <= 64 MB in all; same arguments -> same inputs, run after run")
     ap.add_argument("--latency-steps", type=int, default=32,
-                    help="after the throughput pass, time this many batch-1 decode steps through the same "
+                    help="--full: after the throughput pass, time this many batch-1 decode steps through the same "
                          "pipeline (b1_p50_tpot_ms / b1_tok_s in the JSON line); 0 = skip")
     ap.add_argument("--mid-batch", type=int, default=128,
-                    help="after the batch-1 pass, time --latency-steps decode steps of this many sequences "
+                    help="--full: after the batch-1 pass, time --latency-steps decode steps of this many sequences "
                          "(<= 128, the fused-GEMV regime; mid_p50_tpot_ms / mid_tok_s); 0 = skip")
     ap.add_argument("--ttft-lens", default="2048",
-                    help="one GPU: after the decode passes, batch-1 time-to-first-token (embed -> all layers -> "
-                         "lm_head argmax, median of 3 after a warm-up) at these prompt lengths on a separate "
-                         "engine of the same model (ttft_prompt_ms in the JSON line); '' or 0 = skip")
+                    help="--full, one GPU: after the decode passes, batch-1 time-to-first-token (embed -> all "
+                         "layers -> lm_head argmax, median of 3 after a warm-up) at these prompt lengths on a "
+                         "separate engine of the same model (ttft_prompt_ms in the JSON line); '' or 0 = skip")
     ap.add_argument("--extras", default="llama3.2-3b,llama2-13b,llama2-70b:10",
-                    help="one GPU: after the headline, short decode runs of these models at the same batch "
+                    help="--full, one GPU: after the headline, short decode runs of these models at the same batch "
                          "(MODEL or MODEL:LAYERS = one stage of that many layers with 8 micro-batches, e.g. "
                          "the 70B 8-stage plan's 10-layer stage) -> 'extra' in the JSON line; '' = skip")
     ap.add_argument("--stage-layers", type=int, default=0,
@@ -337,6 +348,37 @@ def extra_runs(spec: str, a) -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(outputs: dict, folder: str, seed: int = 0) -> dict:
+    """Write each array of ``outputs`` (name -> host tensor) as ``folder/<name>.npy``: integers as
+    float64 (exact up to 2^53), the rest as float32. An array above its equal share of
+    DUMP_BUDGET_BYTES is cut to a fixed sample of its rows (all leading dimensions flattened),
+    drawn by a generator seeded with ``seed`` and the array's name only - so two builds sample
+    the same rows -, and the chosen row numbers go to ``<name>.rows.npy``. Returns name -> shape."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(outputs)) - 4096  # room for the .npy header and the row list
+    shapes = {}
+    for name in sorted(outputs):
+        t = outputs[name]
+        arr = t.numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+        if arr.nbytes > share and arr.ndim >= 1:
+            rows = arr.reshape(-1, arr.shape[-1]) if arr.ndim > 1 else arr.reshape(-1, 1)
+            row_bytes = rows.shape[1] * rows.itemsize + 8
+            keep = max(1, share // row_bytes)
+            rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+            idx = np.sort(rng.choice(rows.shape[0], size=min(keep, rows.shape[0]), replace=False))
+            arr = np.ascontiguousarray(rows[idx])
+            np.save(os.path.join(folder, f"{name}.rows.npy"), idx.astype(np.float64))
+        np.save(os.path.join(folder, f"{name}.npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
+
+
 def main():
     _die_with_parent()  # a child of spawn_ranks / supervise: die with that parent
     a = parse()
@@ -354,10 +396,12 @@ def main():
                                batch=a.batch, prompt_len=a.prompt_len, max_seq=a.max_seq,
                                microbatches=a.microbatches, seed=a.seed, use_graph=not a.no_graph,
                                weight_dtype=a.weight_dtype, streams=a.streams, dp=a.dp,
-                               latency_steps=a.latency_steps, device=a.device, stage_layers=a.stage_layers,
-                               transport=a.transport, mid_batch=a.mid_batch)
+                               latency_steps=a.latency_steps if a.full else 0, device=a.device,
+                               stage_layers=a.stage_layers, transport=a.transport,
+                               mid_batch=a.mid_batch if a.full else 0, collect_outputs=bool(a.dump_outputs))
     if res is None:  # non-zero ranks
         return
+    dumped = dump_outputs(res["outputs"], a.dump_outputs, a.seed) if a.dump_outputs else None
     line = {
         "metric": "stage_profile_tokens_per_sec" if a.stage_layers else "output_tokens_per_sec_whole_node",
         "value": round(res["tok_s"], 2),
@@ -397,14 +441,16 @@ def main():
     topo = res.get("topology")
     if topo:  # proof of placement: process-group size, each rank's device UUID / PCI id, edge transports
         line["dist"] = topo
-    lens = [int(x) for x in str(a.ttft_lens).split(",") if x.strip() and int(x) > 0]
+    if dumped is not None:
+        line["dumped_outputs"] = dumped  # name -> shape of the files under --dump-outputs
+    lens = [int(x) for x in str(a.ttft_lens).split(",") if x.strip() and int(x) > 0] if a.full else []
     if lens and a.gpus == 1 and a.device == "cuda" and not a.stage_layers:
         try:
             line["ttft_prompt_ms"] = ttft_probe(a.model, lens, seed=a.seed)
         except Exception as e:  # never lose the headline line to the side measurement
             line["ttft_prompt_ms"] = None
             line["ttft_error"] = f"{type(e).__name__}: {e}"[:200]
-    if a.extras and a.gpus == 1 and a.device == "cuda" and not a.stage_layers:
+    if a.full and a.extras and a.gpus == 1 and a.device == "cuda" and not a.stage_layers:
         line["extra"] = extra_runs(a.extras, a)
     from llm_sharding_amd.utils.runtime_config import knobs_in_effect
     line["knobs"] = knobs_in_effect()  # LSA_* switches set for this run ({} = the product defaults)

@@ -146,24 +146,52 @@ void late_bind() {
 }
 
 void teardown_while_sending() {
+  // Paced by progress, not by the clock: the push queue and the pull's frame queue are
+  // unbounded, and free-running senders around a sleeping main thread queued gigabytes when
+  // the host was busy and the sleep ran long (the process was then killed for its memory).
+  // A sender runs at most kAhead messages ahead of what the main thread has taken from the
+  // pull, and queues kAfter more against the dead peer once the pull is gone.
+  constexpr int kSenders = 3, kAhead = 128, kWarm = 300, kAfter = 64;
   int port = 0;
   void* pull = lsa_pull_bind("127.0.0.1", 0, &port);
   std::vector<void*> pushes;
-  for (int s = 0; s < 3; ++s) pushes.push_back(lsa_push_connect("127.0.0.1", port));
-  std::atomic<bool> go{true};
+  for (int s = 0; s < kSenders; ++s) pushes.push_back(lsa_push_connect("127.0.0.1", port));
+  std::atomic<bool> go{true}, closed{false};
+  std::atomic<long long> sent{0}, taken{0};
+  std::atomic<int> finished{0};
   std::vector<std::thread> th;
-  for (int s = 0; s < 3; ++s)
+  for (int s = 0; s < kSenders; ++s)
     th.emplace_back([&, s] {
-      int i = 0;
+      int i = 0, extra = 0;
       while (go.load()) {
+        const bool gone = closed.load();
+        if (gone ? extra >= kAfter : sent.load() - taken.load() >= kAhead) {
+          std::this_thread::sleep_for(std::chrono::microseconds(50));
+          continue;
+        }
         const std::string m = payload(s, i++ % 64);
         if (lsa_push_send(pushes[s], m.data(), (long long)m.size()) != 0) break;
-        if (i % 64 == 0) std::this_thread::sleep_for(std::chrono::microseconds(50));
+        if (!gone) {
+          ++sent;
+        } else if (++extra == kAfter) {
+          ++finished;
+        }
       }
     });
-  std::this_thread::sleep_for(std::chrono::milliseconds(50));
-  lsa_pull_close(pull);  // peers see the connection drop and keep retrying
-  std::this_thread::sleep_for(std::chrono::milliseconds(50));
+  std::string got;
+  while (taken.load() < kWarm) {
+    CHECK(recv_one(pull, got, 30000));
+    ++taken;
+  }
+  // the senders are mid-stream (the last take let them go on) and up to kAhead frames are in
+  // flight or queued untaken: peers see the connection drop and keep retrying
+  lsa_pull_close(pull);
+  closed = true;
+  for (int waited_ms = 0; finished.load() < kSenders; ++waited_ms) {
+    CHECK(waited_ms < 30000);
+    std::this_thread::sleep_for(std::chrono::milliseconds(1));
+  }
+  for (void* p : pushes) (void)lsa_push_pending(p);  // status query while the writers retry
   go = false;
   for (auto& t : th) t.join();
   for (void* p : pushes) lsa_push_close(p);

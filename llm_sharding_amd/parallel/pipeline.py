@@ -678,6 +678,28 @@ def _latency_pass(cfg, stage: "PipelineStage", srank: int, pp: int, st, dev, max
     return (_percentile(tp, 0.5) if tp else 0.0), el
 
 
+def last_step_outputs(stage: "PipelineStage", tokens_mb0) -> dict:
+    """Host copies of what a caller of the decode path holds after the last step of a drained
+    phase, on the stage that owns the token ids (a single stage, or stage 0 of a pipeline):
+      ``tokens_last_step``  [M, B] the id every sequence produced in that step;
+      ``hidden_last_step``  [n, B, H] this stage's output hidden state of that step, for the
+                            micro-batches whose scratch set no later micro-batch rewrote (the
+                            last ``streams`` ones; all of them at one micro-batch per stream);
+      ``tokens_mb0``        [B, n_tok] the first n_tok ids micro-batch 0 generated, the prefill's
+                            included (the parity digest's input)."""
+    out = {}
+    if stage.world == 1 or stage.first:
+        toks = [stage.final_tokens[mb] if stage.split else g.tokens for mb, g in enumerate(stage.graphs)]
+        if all(t is not None for t in toks):
+            out["tokens_last_step"] = torch.stack([t.reshape(-1).to(torch.int64).cpu() for t in toks])
+    keep = [g for mb, g in enumerate(stage.graphs) if mb >= stage.M - stage.S and g.out_hidden is not None]
+    if keep:
+        out["hidden_last_step"] = torch.stack([g.out_hidden.reshape(stage.B, -1).float().cpu() for g in keep])
+    if tokens_mb0 is not None:
+        out["tokens_mb0"] = torch.tensor(tokens_mb0, dtype=torch.int64)
+    return out
+
+
 def rank_identity(rank: int, dev: torch.device) -> dict:
     """Which device this rank really runs on: host, pid, visibility env and, on a GPU, the
     device's UUID and PCI address (from the HIP runtime, not from the rank number) - so a
@@ -743,7 +765,8 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
                          microbatches: int = 0, seed: int = 0, use_graph: bool = True,
                          verbose: bool = True, weight_dtype: str = "bf16", streams: int = 1,
                          device: str = "cuda", dp: int = 1, latency_steps: int = 0,
-                         stage_layers: int = 0, transport: str = "rccl", mid_batch: int = 0) -> Optional[dict]:
+                         stage_layers: int = 0, transport: str = "rccl", mid_batch: int = 0,
+                         collect_outputs: bool = False) -> Optional[dict]:
     """``microbatches`` 0 = ``streams`` x stages (every GPU holds ``streams`` micro-batches of
     ``batch`` sequences: weak scaling); ``max_seq`` 0 = what the run needs, rounded up to 64.
 
@@ -767,7 +790,10 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     receiver's HBM (parallel/ipc_ring.py: one kernel per send / receive, device flags, no
     communicator); the process group is then gloo (barriers and the final statistics only), so
     N ranks may also share ONE GPU (``LOCAL_RANK % device_count``) - a multi-process rehearsal
-    of the exact N-stage pipeline on a 1-GPU box. A timed-out hand-off raises (exit non-zero)."""
+    of the exact N-stage pipeline on a 1-GPU box. A timed-out hand-off raises (exit non-zero).
+
+    ``collect_outputs``: rank 0's result carries ``outputs``, host copies of what the LAST timed
+    step left on its stage, taken before any later pass reuses the engine (``last_step_outputs``)."""
     cfg = get_preset(model)
     if stage_layers:
         import dataclasses
@@ -916,6 +942,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
         else:  # row k = token produced at decode step k, after the prefill's first token
             tokens_mb0 = torch.cat([firsts[0].cpu()[None].to(hist.dtype), hist[:n_tok - 1]]).T.tolist() \
                 if firsts else None
+    outputs = last_step_outputs(stage, tokens_mb0) if collect_outputs and rank == 0 else None
 
     # batch-1 latency pass (the reference's only mode, node_worker.py:493-559): ONE sequence
     # through the same pipeline and weights, a 1-row decode graph per stage
@@ -988,6 +1015,8 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
         "mem_pred_gb": round(mem_pred_max / 1e9, 2),
         "mem_peak_gb": round(mem_peak_max / 1e9, 2) if gpu else None,
     }
+    if outputs is not None:
+        res["outputs"] = outputs
     trace = tracing.export_env(stage.tl)
     if trace and verbose:
         print(f"[bench] rank {rank} timeline -> {trace}  {stage.tl.summary()}", flush=True)

@@ -11,7 +11,8 @@
 # tasks:
 #   tests [PYTEST ARGS]          GPU suite (pytest -m gpu -x, per-test thread timeout), e.g. tests -k gemm
 #   smoke                        __graft_entry__.smoke()
-#   bench [BENCH ARGS]           python bench.py ARGS (default: the driver's --steps 20 --warmup 5)
+#   bench [BENCH ARGS]           python bench.py ARGS (default: the driver's --steps 20 --warmup 5; add --full
+#                                for the latency passes, the TTFT probe and the other models)
 #   ab ROUNDS ENV_A ENV_B [ARGS] bench.py alternated A / B ROUNDS times (ENV_x: "K=V K2=V2" or "-")
 #   trace [BENCH ARGS]           rocprofv3 --kernel-trace --stats over bench.py (no PMC in the same run)
 #   pmc COUNTERS SCRIPT [ARGS]   one rocprofv3 --pmc pass (COUNTERS comma-separated) over a python script

@@ -26,7 +26,7 @@ def _run_bench(*args, timeout=300):
     return json.loads(lines[0])
 
 
-COMMON = ["--steps", "3", "--warmup", "2", "--batch", "2", "--prompt-len", "4", "--latency-steps", "2"]
+COMMON = ["--steps", "3", "--warmup", "2", "--batch", "2", "--prompt-len", "4", "--full", "--latency-steps", "2"]
 
 
 def test_bench_cli_single_rank():
@@ -35,6 +35,35 @@ def test_bench_cli_single_rank():
     assert line["metric"] == "output_tokens_per_sec_whole_node" and line["value"] > 0
     assert line["config"]["parallelism"] == "pp1"
     assert line["b1_p50_tpot_ms"] > 0 and line["b1_tok_s"] > 0
+
+
+def test_bench_cli_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full only the headline is measured (the side measurements' keys are null or
+    absent, whatever their own options say), --steps sets the number of timed steps, and
+    --dump-outputs writes the last timed step's outputs as float .npy files that a second run
+    with the same arguments reproduces exactly."""
+    import numpy as np
+    args = ["--gpus", "1", "--model", "tiny", "--steps", "3", "--warmup", "2", "--batch", "2", "--prompt-len", "4",
+            "--latency-steps", "2"]
+    dumps = []
+    for d in ("a", "b"):
+        line = _run_bench(*args, "--dump-outputs", str(tmp_path / d))
+        assert line["metric"] == "output_tokens_per_sec_whole_node" and line["value"] > 0 and line["steps"] == 3
+        assert line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["dtype"] == "bf16"
+        assert line["b1_p50_tpot_ms"] is None and line["b1_tok_s"] is None and line["mid_tok_s"] is None
+        assert "extra" not in line and "ttft_prompt_ms" not in line
+        files = sorted(p.name for p in (tmp_path / d).iterdir())
+        assert files == ["hidden_last_step.npy", "tokens_last_step.npy", "tokens_mb0.npy"], files
+        dumps.append({f[:-len(".npy")]: np.load(tmp_path / d / f) for f in files})
+        assert sum(v.nbytes for v in dumps[-1].values()) <= 64 * 1000 * 1000
+    a, b = dumps
+    assert a["tokens_last_step"].shape == (1, 2) and a["tokens_last_step"].dtype == np.float64
+    assert a["tokens_mb0"].shape == (2, 5)  # warm-up + timed steps of each of the 2 sequences
+    assert a["hidden_last_step"].dtype == np.float32 and a["hidden_last_step"].shape[:2] == (1, 2)
+    assert np.isfinite(a["hidden_last_step"]).all() and np.abs(a["hidden_last_step"]).max() > 0
+    assert (a["tokens_last_step"] >= 0).all() and (a["tokens_last_step"] == np.round(a["tokens_last_step"])).all()
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
 
 
 @pytest.mark.parametrize("n", [2, 8])
