@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""Single-process greedy generation (reference inference.py, which calls HF generate): the
-whole model on one device through the MI355X engine (hipGraph decode on GPU).
+"""Single-process generation (reference inference.py, which calls HF generate): the whole model
+on one device through the MI355X engine (hipGraph decode on GPU). Greedy by default;
+``--temperature T [--top-k K] [--top-p P] [--seed S]`` samples on the device instead (the
+``do_sample / top_p / temperature`` switches of the reference's generate call), reproducibly:
+the seed in use is printed, and the same seed gives the same tokens.
 
     python inference.py --shards DIR [--prompt "..."] [--max-new-tokens 128]
     python inference.py --random llama2-7b --max-new-tokens 64     # random-init weights
     python inference.py --shards DIR --hf-compare HF_DIR           # + the reference's own path
+    python inference.py --shards DIR --temperature 0.7 --top-p 0.9 --seed 1
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
 (/root/reference/inference.py:16-45: transformers' AutoModelForCausalLM + greedy generate) on the
@@ -24,7 +28,7 @@ from llm_sharding_amd.models.tokenizer import SyntheticByteTokenizer, load_token
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, ShardFolderSource, StageEngine  # noqa: E402
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shards", default="")
     ap.add_argument("--random", default="", help="preset name for random-init weights (no checkpoint)")
@@ -33,7 +37,27 @@ def main():
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--hf-compare", default="", help="HF checkpoint dir: also run transformers' greedy generate "
                                                      "(the reference inference.py's path, fp32 CPU) and compare tokens")
-    a = ap.parse_args()
+    ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy decode")
+    ap.add_argument("--top-k", type=int, default=0, help="keep the k most likely tokens (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="keep the smallest set of mass >= p (1: off)")
+    ap.add_argument("--seed", type=int, default=None, help="64-bit sampling seed (default: drawn and printed)")
+    return ap
+
+
+def sampling_from_args(a):
+    """The run's SamplingParams; None for the greedy default (temperature 0)."""
+    from llm_sharding_amd.runtime.sampling import SamplingParams
+    if a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None:
+        return None
+    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed)
+    return None if sp.greedy else sp
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    sp = sampling_from_args(a)
+    if sp is not None and a.hf_compare:
+        raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling flags")
     if a.shards:
         cfg = LlamaConfig.from_pretrained(a.shards)
         src, tok = ShardFolderSource(a.shards, cfg), load_tokenizer(a.shards)
@@ -49,6 +73,9 @@ def main():
     slot, pos = eng.prefill_rows([0], [ids.numel()])
     h = eng.forward(eng.embed(ids.to(a.device)), slot, pos)
     eng.advance([0], [ids.numel()])
+    if sp is not None:
+        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp)
+        return report(a, cfg, tok, ids, out, dt_s)
     first = eng.head(h, [ids.numel() - 1])
     out = [int(first[0])]
     t1 = time.perf_counter()
@@ -69,6 +96,29 @@ def main():
             cur = eng.head(h)
             out.append(int(cur[0]))
     dt_s = time.perf_counter() - t1
+    return report(a, cfg, tok, ids, out, dt_s)
+
+
+def sample_tokens(eng, h, n_prompt: int, n_new: int, sp) -> tuple:
+    """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
+    hidden): the first token from ``Sampler.sample``, the rest from a captured
+    ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU)."""
+    from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, Sampler, SamplingDecodeGraph
+    print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
+    first = Sampler(eng).sample(h, [n_prompt - 1], [sp], [n_prompt])
+    t1 = time.perf_counter()
+    g = (SamplingDecodeGraph if eng.gpu else EagerSamplingDecode)(eng, 1, "full", history_len=max(1, n_new - 1))
+    g.set_params(0, sp)
+    g.tokens.copy_(first.to(torch.int32))
+    g.capture()
+    for _ in range(n_new - 1):
+        g.replay()
+    if eng.gpu:
+        torch.cuda.synchronize()
+    return [int(first[0])] + g.history[:n_new - 1, 0].tolist(), time.perf_counter() - t1
+
+
+def report(a, cfg, tok, ids, out, dt_s):
     eos = [i for i, t in enumerate(out) if t in cfg.eos_ids]
     if eos:
         out = out[:eos[0] + 1]

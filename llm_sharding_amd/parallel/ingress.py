@@ -11,6 +11,7 @@ import json
 import threading
 from typing import Callable, Optional
 
+from ..runtime.sampling import SamplingParams
 from . import protocol
 from .transport import Again, PullSocket, PushSocket
 
@@ -74,7 +75,9 @@ def decode_message(raw: bytes) -> dict:
 
 def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies) -> int:
     """Submit every prompt of a ``user_request`` message (``input_ids``: one list or a batch of
-    lists, else ``text`` through the tokenizer). Returns the number of requests queued."""
+    lists, else ``text`` through the tokenizer; optional ``temperature``, ``top_k``, ``top_p``,
+    ``seed``: sampling instead of greedy decode, a batch's prompts each drawing their own seed
+    when none is given). Returns the number of requests queued."""
     n_new = int(msg.get("max_new_tokens") or default_new)
     rows = msg.get("input_ids")
     if rows is None:
@@ -87,7 +90,10 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     n = 0
     for ids in rows:
         try:
-            srv.submit(ids, n_new, on_token=replies, reply_to=msg.get("reply_to"))
+            # optional temperature / top_k / top_p / seed keys; absent: greedy (the plain call)
+            sp = SamplingParams.from_dict(msg)
+            kw = {} if sp is None else {"sampling": sp}
+            srv.submit(ids, n_new, on_token=replies, reply_to=msg.get("reply_to"), **kw)
             n += 1
         except ValueError as e:
             replies.error(msg.get("reply_to"), f"request rejected: {e}")

@@ -43,6 +43,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from ..runtime.engine import DecodeGraph, StageEngine
+from ..runtime.sampling import SamplingParams
 from ..utils import tracing
 from .pipeline import DistP2P, _percentile
 
@@ -58,6 +59,7 @@ class Request:
     eos_ids: tuple
     on_token: Optional[Callable] = None
     reply_to: Optional[str] = None
+    sampling: Optional[SamplingParams] = None  # None: greedy
     state: str = WAITING
     slot: int = -1
     prefilled: int = 0
@@ -136,6 +138,10 @@ class PipelineServer:
         # GPU at once (see pipeline.PipelineStage); a micro-batch's own commands stay ordered.
         self.S = max(1, min(streams, microbatches)) if (self.graph_mode and world == 1) else 1
         self.streams = [torch.cuda.Stream(self.device) for _ in range(self.S)] if self.S > 1 else []
+        # sampling (world == 1): off until the first non-greedy request is admitted - an all-greedy
+        # server never builds a Sampler, a sampling graph or a logits buffer
+        self.sampling_on = False
+        self.sampler = None
         self._build_graphs()
         # rank 0 state
         self.incoming: "queue.Queue[Request]" = queue.Queue()
@@ -169,10 +175,49 @@ class PipelineServer:
         if self.graph_mode:
             mode = "full" if self.world == 1 else ("first" if self.first else ("last" if self.last else "mid"))
             for mb in range(self.M):
-                self.graphs.append(DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb),
-                                               scratch=mb % self.S).capture())
+                if self.sampling_on:
+                    from ..runtime.sampling import SamplingDecodeGraph
+                    g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
+                else:
+                    g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
+                self.graphs.append(g.capture())
         for st in self.streams:  # after weight loading and graph capture on the current stream
             st.wait_stream(torch.cuda.current_stream(self.device))
+
+    def _enable_sampling(self) -> None:
+        """First non-greedy request (world == 1): build the Sampler and, in graph mode, replace
+        every micro-batch's greedy graph by a SamplingDecodeGraph that takes over its device
+        positions and tokens. Rows start greedy; a slot's parameters are written on admission.
+        From here on greedy requests of this server take the arg-max of the bf16 logits in the
+        decode graph (the first token still comes from the fused argmax)."""
+        from ..runtime.sampling import Sampler, SamplingDecodeGraph
+        self.sampler = Sampler(self.eng)
+        self.sampling_on = True
+        if not self.graph_mode:
+            return
+        torch.cuda.synchronize(self.device)
+        old, self.graphs = self.graphs, []
+        for mb in range(self.M):
+            g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S)
+            g.pos.copy_(old[mb].pos)
+            g.tokens.copy_(old[mb].tokens)
+            self.graphs.append(g.capture())
+        del old
+        for st in self.streams:
+            st.wait_stream(torch.cuda.current_stream(self.device))
+        torch.cuda.synchronize(self.device)
+
+    def _sample_rows(self, h, rows_idx, slots, positions, tok: torch.Tensor) -> torch.Tensor:
+        """Replace the greedy tokens ``tok`` of the rows whose request samples: row
+        ``rows_idx[i]`` of ``h`` belongs to ``slots[i]`` and its new token will sit at
+        ``positions[i]``."""
+        reqs = [self.by_slot.get(s) for s in slots]
+        sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
+        if sel:
+            t = self.sampler.sample(h, [rows_idx[i] for i in sel], [reqs[i].sampling for i in sel],
+                                    [positions[i] for i in sel])
+            tok[torch.tensor(sel, dtype=torch.long, device=tok.device)] = t.to(tok.dtype)
+        return tok
 
     def _reshard(self, start: int, end: int) -> None:
         """Every rank, pipeline drained: free this stage's engine, load layers [start, end),
@@ -187,6 +232,9 @@ class PipelineServer:
                 torch.cuda.empty_cache()
             self.eng = self._build_engine(start, end)
             self.start, self.end = start, end
+            if self.sampling_on:
+                from ..runtime.sampling import Sampler
+                self.sampler = Sampler(self.eng)
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
@@ -311,6 +359,13 @@ class PipelineServer:
                 if not emit_rows:
                     return []
                 tok = eng.head(h, emit_rows).to(torch.int32)
+                if self.sampling_on:
+                    em = [it for it in items if it[3]]
+                    tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok)
+                    if self.graph_mode:  # the slot's parameters, before its first decode step
+                        for (s, _, _, _) in em:
+                            r = self.by_slot.get(s)
+                            self.graphs[mb].set_params(s - mb * self.B, None if r is None else r.sampling)
                 if self.world == 1:
                     return self._to_host(tok)
                 self._send(tok.contiguous(), 0)
@@ -347,6 +402,8 @@ class PipelineServer:
                 eng.seq_len[s] = p + 1
             if self.last:
                 tok = eng.head(h).to(torch.int32)
+                if self.sampling_on:
+                    tok = self._sample_rows(h, list(range(n)), slots, [p + 1 for p in pos], tok)
                 if self.world == 1:
                     return self._to_host(tok)
                 self._send(tok.contiguous(), 0)
@@ -357,10 +414,17 @@ class PipelineServer:
 
     # ------------------------------------------------------------------ rank 0: requests
     def submit(self, input_ids, max_new_tokens: int = 64, eos_ids=None, on_token=None,
-               reply_to: Optional[str] = None) -> int:
-        """Queue a request (thread-safe). ``input_ids``: list of token ids."""
+               reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> int:
+        """Queue a request (thread-safe). ``input_ids``: list of token ids. ``sampling``:
+        temperature / top-k / top-p / seed of the request (None or temperature 0: greedy); its
+        output depends only on its own prompt and seed, not on the slot or batch it runs in."""
         if not self.first:
             raise RuntimeError("requests are submitted on rank 0 (the ingress stage)")
+        if sampling is not None and sampling.greedy:
+            sampling = None
+        if sampling is not None and self.world > 1:
+            raise ValueError("sampling (temperature > 0) needs a single-stage server: with more than one pipeline "
+                             "stage only greedy requests are served")
         ids = [int(x) for x in input_ids]
         if not ids:
             raise ValueError("empty prompt")
@@ -371,7 +435,7 @@ class PipelineServer:
             rid = self._next_id
             self._next_id += 1
         eos = tuple(self.cfg.eos_ids if eos_ids is None else eos_ids)
-        r = Request(rid, ids, int(max_new_tokens), eos, on_token=on_token, reply_to=reply_to,
+        r = Request(rid, ids, int(max_new_tokens), eos, on_token=on_token, reply_to=reply_to, sampling=sampling,
                     t_submit=time.perf_counter())
         self.incoming.put(r)
         return rid
@@ -471,6 +535,8 @@ class PipelineServer:
             if not self.waiting or self._replan is not None:
                 break
             r = self.waiting.pop(0)
+            if r.sampling is not None and not self.sampling_on:
+                self._enable_sampling()
             r.slot, r.state, r.prefilled = s, PREFILLING, 0
             self.by_slot[s] = r
             if s in resets:
@@ -601,4 +667,4 @@ class PipelineServer:
         }
 
 
-__all__ = ["PipelineServer", "Request"]
+__all__ = ["PipelineServer", "Request", "SamplingParams"]

@@ -1,0 +1,257 @@
+"""Seeded temperature / top-k / top-p sampling on top of :class:`StageEngine`.
+
+Greedy decode (``StageEngine.head``, ``DecodeGraph``) is untouched: everything here is an extra
+path that exists only when a request asks for it.
+
+* :class:`SamplingParams` - one request's ``temperature / top_k / top_p / seed``.
+* :class:`Sampler` - bf16 logits of selected rows through the existing lm_head kernels
+  (``EPI_STORE``) and one sampled token per row (``ops.sampling.sample``; the fp64 reference on
+  a CPU engine). Used for the first token after a prefill.
+* :class:`SamplingDecodeGraph` - a :class:`DecodeGraph` whose step ends in logits ->
+  ``lsa_sample`` -> ``argmax_finalize`` instead of the fused argmax, with per-row parameters on
+  the device (:meth:`SamplingDecodeGraph.set_params` between replays).
+* :class:`EagerSamplingDecode` - the same interface for CPU engines.
+
+A request's tokens depend only on its own logits, seed and positions (the noise is a pure
+function of seed, position and vocabulary index), not on the row, slot or batch it runs in.
+"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import torch
+
+from ..ops import sampling as S
+from .engine import DecodeGraph, EagerDecode, StageEngine
+
+
+@dataclass
+class SamplingParams:
+    """``temperature == 0`` is greedy (the filters are then ignored). ``top_k == 0`` and
+    ``top_p == 1`` switch the filters off. ``seed=None`` draws 64 bits from ``os.urandom`` and
+    stores them, so any run can be replayed from ``params.seed``."""
+    temperature: float = 0.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        self.temperature, self.top_k, self.top_p = float(self.temperature), int(self.top_k), float(self.top_p)
+        if not self.temperature >= 0.0 or self.temperature == float("inf"):
+            raise ValueError(f"temperature must be a finite value >= 0, got {self.temperature}")
+        if self.top_k < 0 or self.top_k >= 1 << 31:
+            raise ValueError(f"top_k must be >= 0 (0 = off), got {self.top_k}")
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p}")
+        if self.seed is None:
+            self.seed = int.from_bytes(os.urandom(8), "little")
+        self.seed = int(self.seed)
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"seed must be a 64-bit unsigned value, got {self.seed}")
+
+    @property
+    def greedy(self) -> bool:
+        return self.temperature == 0.0
+
+    @classmethod
+    def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
+        """``temperature / top_k / top_p / seed`` keys of a request dict; None (greedy) when
+        none of them is present."""
+        keys = ("temperature", "top_k", "top_p", "seed")
+        if not any(d.get(k) is not None for k in keys):
+            return None
+        return cls(**{k: d[k] for k in keys if d.get(k) is not None})
+
+
+GREEDY = SamplingParams(0.0, 0, 1.0, 0)
+
+
+def _check_full_head(eng: StageEngine) -> None:
+    if eng.lm_head is None:
+        raise RuntimeError("[ERROR] this stage has no lm_head")
+    if (eng.head_v0, eng.head_v1) != (0, eng.cfg.head_rows):
+        raise NotImplementedError("sampling needs the whole lm_head on one stage: this stage holds only vocabulary "
+                                  f"rows [{eng.head_v0}, {eng.head_v1}) of {eng.cfg.head_rows} (split head)")
+
+
+class Sampler:
+    """Logits and sampled tokens of a stage that holds the whole lm_head."""
+
+    def __init__(self, eng: StageEngine):
+        _check_full_head(eng)
+        self.eng = eng
+
+    # ------------------------------------------------------------------ logits
+    def logits(self, h: torch.Tensor, rows_idx=None) -> torch.Tensor:
+        """final norm -> lm_head of the selected rows: bf16 ``[n, head_rows]`` (columns
+        ``>= vocab_size`` are padding)."""
+        eng = self.eng
+        if rows_idx is None:
+            rows_idx = list(range(h.shape[0]))
+        if not eng.gpu:
+            hs = h[torch.as_tensor(rows_idx, device=h.device, dtype=torch.long)]
+            return eng.logits_torch(hs).to(torch.bfloat16)
+        idx = eng._i32(rows_idx)
+        out = torch.empty((idx.numel(), eng.cfg.head_rows), dtype=torch.bfloat16, device=eng.device)
+        self.logits_into(h, idx.numel(), out, a_rows=idx)
+        return out
+
+    def logits_into(self, h: torch.Tensor, rows: int, out: torch.Tensor, a_rows: Optional[torch.Tensor] = None) -> None:
+        """GPU: logits of ``rows`` rows of ``h`` (``a_rows``: int32 row gather) into bf16 ``out``
+        [>= rows, head_rows], on the existing projection kernels with the EPI_STORE epilogue -
+        the kernel family per row count mirrors ``StageEngine.head_gemv``."""
+        from ..ops import hip
+        eng, cfg = self.eng, self.eng.cfg
+        N, H, eps, D = cfg.head_rows, cfg.hidden_size, cfg.rms_norm_eps, eng.DECODE_MAX_ROWS
+        if out.dtype != torch.bfloat16 or out.shape[0] < rows or out.shape[1] != N:
+            raise ValueError(f"logits_into: out must be bf16 [>= {rows}, {N}]")
+        ep = hip.make_epi(out=out, ldo=out.stride(0), bias=eng.head_bias)
+        if rows > D and (not cfg.is_gpt2 and eng.lm_head_s is None and eng.sk_ws is not None and N % 128 == 0
+                         and rows <= eng.buf_xn.shape[0]):
+            xn = eng.buf_xn[:rows]
+            src = h[:rows] if a_rows is None else h.index_select(0, a_rows.long())
+            hip.rmsnorm(src, None, xn, rows, eps, H)
+            hip.gemm_sk(xn, eng.lm_head, rows, N, H, hip.EPI_STORE, ep, ws=eng.sk_ws)
+            return
+        if rows > D:  # the GEMV kernels take <= 128 rows per launch
+            for c0 in range(0, rows, D):
+                c = min(D, rows - c0)
+                if a_rows is None:
+                    self.logits_into(h[c0:c0 + c], c, out[c0:c0 + c])
+                else:
+                    self.logits_into(h, c, out[c0:c0 + c], a_rows=a_rows[c0:c0 + c])
+            return
+        if cfg.is_gpt2:  # ln_f (mean + bias) runs as its own kernel in front of a plain GEMV
+            xn = eng.buf_xn[:rows]
+            src = h if a_rows is None else h.index_select(0, a_rows.long())
+            hip.layernorm(src, xn, eng.final_norm, eng.final_norm_b, rows, eps)
+            if eng.lm_head_s is not None:
+                hip.proj_fp8(xn, eng.lm_head.view(-1), eng.lm_head_s, rows, N, H, hip.EPI_STORE, ep, ws=eng.coop_ws)
+            else:
+                hip.gemv(xn, eng.lm_head, rows, N, H, hip.EPI_STORE, ep, ws=eng.coop_ws)
+            return
+        if eng.lm_head_s is not None:
+            hip.proj_fp8(h, eng.lm_head.view(-1), eng.lm_head_s, rows, N, H, hip.EPI_STORE, ep, norm=True, eps=eps,
+                         a_rows=a_rows, ws=eng.coop_ws)
+        else:
+            hip.gemv(h, eng.lm_head, rows, N, H, hip.EPI_STORE, ep, ws=eng.coop_ws, norm=True, eps=eps, a_rows=a_rows)
+
+    # ------------------------------------------------------------------ tokens
+    def sample_logits(self, logits: torch.Tensor, params_list: Sequence[SamplingParams], positions) -> torch.Tensor:
+        """One token per row of bf16 ``logits`` [n, >= vocab_size]; ``positions[i]`` is the
+        position the sampled token will occupy (its Philox counter). Returns int64 [n]."""
+        eng, V = self.eng, self.eng.cfg.vocab_size
+        n = logits.shape[0]
+        positions = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
+        if len(params_list) != n or len(positions) != n:
+            raise ValueError(f"sample: {n} rows, {len(params_list)} params, {len(positions)} positions")
+        if not eng.gpu:
+            tok, _, _, _ = S.sample_reference(logits.to(torch.bfloat16), V, [p.temperature for p in params_list],
+                                              [p.top_k for p in params_list], [p.top_p for p in params_list],
+                                              [p.seed for p in params_list], positions)
+            return torch.from_numpy(tok)
+        from ..ops import hip
+        dev = eng.device
+        arr = device_params(params_list, dev)
+        ctr = torch.tensor(positions, dtype=torch.int32, device=dev)
+        keys = torch.zeros(n, dtype=torch.int64, device=dev)
+        S.sample(logits, V, n, arr["temperature"], arr["top_k"], arr["top_p"], arr["seed"], ctr, keys)
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+        for c0 in range(0, n, 1024):  # argmax_finalize takes <= 1024 rows
+            c = min(1024, n - c0)
+            hip.argmax_finalize(keys[c0:c0 + c], c, out[c0:c0 + c])
+        return out.long()
+
+    def sample(self, h: torch.Tensor, rows_idx, params_list: Sequence[SamplingParams], positions) -> torch.Tensor:
+        """Sampled tokens (int64 [n]) of the selected rows of the final hidden ``h``: the first
+        token after a prefill uses ``positions[i]`` = the prompt length."""
+        return self.sample_logits(self.logits(h, rows_idx), params_list, positions)
+
+
+def device_params(params_list: Sequence[SamplingParams], device) -> dict:
+    """Per-row device arrays of ``lsa_sample``."""
+    return {
+        "temperature": torch.tensor([p.temperature for p in params_list], dtype=torch.float32, device=device),
+        "top_k": torch.tensor([p.top_k for p in params_list], dtype=torch.int32, device=device),
+        "top_p": torch.tensor([p.top_p for p in params_list], dtype=torch.float32, device=device),
+        "seed": torch.tensor([S.seed_to_i64(p.seed) for p in params_list], dtype=torch.int64, device=device),
+    }
+
+
+class SamplingDecodeGraph(DecodeGraph):
+    """A captured decode step that samples: ... layers -> bf16 logits -> ``lsa_sample`` ->
+    ``argmax_finalize`` (modes ``"full"`` and ``"last"``). Every row starts greedy
+    (``temperature`` 0: the arg-max of the bf16 logits); :meth:`set_params` writes a row's
+    parameters between replays. The row's Philox counter is its device position + 1 - the
+    position the sampled token will occupy - so no host work happens per token.
+
+    The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
+
+    def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
+                 history_len: int = 0, scratch: int = 0):
+        if mode not in ("full", "last"):
+            raise ValueError("SamplingDecodeGraph runs the head: mode 'full' or 'last'")
+        self.sampler = Sampler(eng)
+        super().__init__(eng, rows, mode, slots=slots, history_len=history_len, scratch=scratch)
+        dev = eng.device
+        self.params = [GREEDY] * rows
+        for k, v in device_params(self.params, dev).items():
+            setattr(self, k, v)
+        self.logits = torch.zeros((rows, eng.cfg.head_rows), dtype=torch.bfloat16, device=dev)
+
+    def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
+        """Small host-to-device copies on the current stream (like ``set_positions``)."""
+        p = GREEDY if params is None else params
+        self.params[row] = p
+        self.temperature[row] = p.temperature
+        self.top_k[row] = p.top_k
+        self.top_p[row] = p.top_p
+        self.seed[row] = S.seed_to_i64(p.seed)
+
+    def _step(self) -> None:
+        hip, eng, rows = self._hip, self.eng, self.rows
+        h = eng.buf_h[:rows]
+        if self.mode == "full":
+            hip.embed(self.tokens, eng.embed_w, h)
+        else:
+            h.copy_(self.h_in)
+        eng._forward_hip(h, self.slot, self.pos, None, rows, nsplit=eng.decode_nsplit(rows))
+        self.sampler.logits_into(h, rows, self.logits)
+        S.sample(self.logits, eng.cfg.vocab_size, rows, self.temperature, self.top_k, self.top_p, self.seed, self.pos,
+                 self.keys, ctr_add=1)
+        hip.argmax_finalize(self.keys, rows, self.tokens, self.pos, 1, self.history,
+                            self.step_ctr if self.history is not None else None)
+
+
+class EagerSamplingDecode(EagerDecode):
+    """:class:`SamplingDecodeGraph`'s interface on devices without graphs (CPU engines)."""
+
+    def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0):
+        if mode not in ("full", "last"):
+            raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
+        super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
+        self.sampler = Sampler(eng)
+        self.params = [GREEDY] * rows
+
+    def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
+        self.params[row] = GREEDY if params is None else params
+
+    def _body(self) -> None:
+        eng = self.eng
+        h = eng.embed(self.tokens) if self.mode == "full" else self.h_in
+        slot, pos = eng.prefill_rows(self.slots, [1] * self.rows)
+        h = eng.forward(h, slot, pos)
+        eng.advance(self.slots, [1] * self.rows)
+        tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos])
+        self.tokens.copy_(tok.to(torch.int32))
+        if self.history is not None and self.step < self.history.shape[0]:
+            self.history[self.step] = self.tokens
+        self.step += 1
+        self._out = h
+
+    replay = _body
+
+
+__all__ = ["SamplingParams", "GREEDY", "Sampler", "SamplingDecodeGraph", "EagerSamplingDecode", "device_params"]

@@ -19,7 +19,10 @@ Rank 0 (embedding stage) is the ingress: it accepts ``{"command": "user_request"
 our LSAM framing, see ``utils/node_worker.send_user_request``) on ``--port``, streams every
 finished request to stdout and, if ``reply_to`` is given, pushes ``{"request_id",
 "output_ids", "text", "ttft_ms", "tpot_ms"}`` back to that address. ``{"command":
-"shutdown"}`` drains the queue and stops every rank.
+"shutdown"}`` drains the queue and stops every rank. Optional ``temperature``, ``top_k``,
+``top_p`` and ``seed`` keys of a request sample on the device instead of greedy decode (one
+pipeline stage only); ``--temperature --top-k --top-p`` do the same for the synthetic load test
+(request i seeded with ``--seed`` + i).
 """
 import argparse
 import json
@@ -56,6 +59,10 @@ def main():
     ap.add_argument("--random", default="", help="alias of --model: random-init weights of a preset")
     ap.add_argument("--requests", type=int, default=0, help="synthetic load test: N requests, then exit")
     ap.add_argument("--prompt-len", type=int, default=128)
+    ap.add_argument("--temperature", type=float, default=0.0, help="load test: sample instead of greedy decode "
+                                                                   "(request i uses seed --seed + i; one stage only)")
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
     a = ap.parse_args()
     if a.random:
         a.model = a.random
@@ -108,9 +115,14 @@ def main():
         srv.serve()
     elif a.requests:
         g = torch.Generator().manual_seed(rc.seed + 1)
-        for _ in range(a.requests):
+        for i in range(a.requests):
             ids = torch.randint(3, cfg.vocab_size, (a.prompt_len,), generator=g).tolist()
-            srv.submit(ids, rc.max_new_tokens, eos_ids=())
+            if a.temperature > 0:
+                from llm_sharding_amd.runtime.sampling import SamplingParams
+                srv.submit(ids, rc.max_new_tokens, eos_ids=(),
+                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i))
+            else:
+                srv.submit(ids, rc.max_new_tokens, eos_ids=())
         t0 = time.perf_counter()
         srv.t_start = t0
         srv.serve(stop_when_idle=True)
