@@ -4,11 +4,15 @@ on one device through the MI355X engine (hipGraph decode on GPU). Greedy by defa
 ``--temperature T [--top-k K] [--top-p P] [--seed S]`` samples on the device instead (the
 ``do_sample / top_p / temperature`` switches of the reference's generate call), reproducibly:
 the seed in use is printed, and the same seed gives the same tokens.
+``--repetition-penalty R`` (the reference's commented-out ``repetition_penalty=1.2``),
+``--presence-penalty A`` and ``--frequency-penalty B`` penalise repeated tokens on the device, with
+or without a temperature (temperature 0: the arg-max of the penalised logits).
 
     python inference.py --shards DIR [--prompt "..."] [--max-new-tokens 128]
     python inference.py --random llama2-7b --max-new-tokens 64     # random-init weights
     python inference.py --shards DIR --hf-compare HF_DIR           # + the reference's own path
     python inference.py --shards DIR --temperature 0.7 --top-p 0.9 --seed 1
+    python inference.py --random llama2-7b --repetition-penalty 1.2
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
 (/root/reference/inference.py:16-45: transformers' AutoModelForCausalLM + greedy generate) on the
@@ -41,23 +45,30 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--top-k", type=int, default=0, help="keep the k most likely tokens (0: off)")
     ap.add_argument("--top-p", type=float, default=1.0, help="keep the smallest set of mass >= p (1: off)")
     ap.add_argument("--seed", type=int, default=None, help="64-bit sampling seed (default: drawn and printed)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="> 1 damps tokens of the prompt and the output so far (HF's repetition_penalty; 1: off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0,
+                    help="subtracted from the logit of every token generated so far (0: off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0,
+                    help="subtracted once per time a token has been generated (0: off)")
     return ap
 
 
 def sampling_from_args(a):
-    """The run's SamplingParams; None for the greedy default (temperature 0)."""
+    """The run's SamplingParams; None for the greedy default (temperature 0, no penalty)."""
     from llm_sharding_amd.runtime.sampling import SamplingParams
-    if a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None:
+    pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
+    if a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0):
         return None
-    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed)
-    return None if sp.greedy else sp
+    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen)
+    return None if sp.plain else sp
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     sp = sampling_from_args(a)
     if sp is not None and a.hf_compare:
-        raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling flags")
+        raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling and penalty flags")
     if a.shards:
         cfg = LlamaConfig.from_pretrained(a.shards)
         src, tok = ShardFolderSource(a.shards, cfg), load_tokenizer(a.shards)
@@ -74,7 +85,7 @@ def main(argv=None):
     h = eng.forward(eng.embed(ids.to(a.device)), slot, pos)
     eng.advance([0], [ids.numel()])
     if sp is not None:
-        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp)
+        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist())
         return report(a, cfg, tok, ids, out, dt_s)
     first = eng.head(h, [ids.numel() - 1])
     out = [int(first[0])]
@@ -99,15 +110,23 @@ def main(argv=None):
     return report(a, cfg, tok, ids, out, dt_s)
 
 
-def sample_tokens(eng, h, n_prompt: int, n_new: int, sp) -> tuple:
+def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None) -> tuple:
     """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from ``Sampler.sample``, the rest from a captured
-    ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU)."""
-    from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, Sampler, SamplingDecodeGraph
+    ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
+    sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along."""
+    from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, PenaltyState, Sampler, SamplingDecodeGraph
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
-    first = Sampler(eng).sample(h, [n_prompt - 1], [sp], [n_prompt])
+    pen, kw = None, {}
+    if sp.penalized:
+        print(f"[INFO] penalties: repetition {sp.repetition_penalty} presence {sp.presence_penalty} "
+              f"frequency {sp.frequency_penalty}")
+        pen = PenaltyState(eng, 1)
+        pen.admit(0, prompt_ids)
+        kw = {"penalties": pen}
+    first = Sampler(eng, pen).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if pen is not None else None)
     t1 = time.perf_counter()
-    g = (SamplingDecodeGraph if eng.gpu else EagerSamplingDecode)(eng, 1, "full", history_len=max(1, n_new - 1))
+    g = (SamplingDecodeGraph if eng.gpu else EagerSamplingDecode)(eng, 1, "full", history_len=max(1, n_new - 1), **kw)
     g.set_params(0, sp)
     g.tokens.copy_(first.to(torch.int32))
     g.capture()

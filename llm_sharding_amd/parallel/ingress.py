@@ -77,7 +77,9 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     """Submit every prompt of a ``user_request`` message (``input_ids``: one list or a batch of
     lists, else ``text`` through the tokenizer; optional ``temperature``, ``top_k``, ``top_p``,
     ``seed``: sampling instead of greedy decode, a batch's prompts each drawing their own seed
-    when none is given). Returns the number of requests queued."""
+    when none is given; optional ``repetition_penalty``, ``presence_penalty``,
+    ``frequency_penalty``: penalties on repeated tokens, with or without a temperature). Returns
+    the number of requests queued."""
     n_new = int(msg.get("max_new_tokens") or default_new)
     rows = msg.get("input_ids")
     if rows is None:
@@ -90,7 +92,7 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     n = 0
     for ids in rows:
         try:
-            # optional temperature / top_k / top_p / seed keys; absent: greedy (the plain call)
+            # optional temperature / top_k / top_p / seed / *_penalty keys; absent: greedy (the plain call)
             sp = SamplingParams.from_dict(msg)
             kw = {} if sp is None else {"sampling": sp}
             srv.submit(ids, n_new, on_token=replies, reply_to=msg.get("reply_to"), **kw)

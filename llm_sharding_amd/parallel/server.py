@@ -142,6 +142,8 @@ class PipelineServer:
         # server never builds a Sampler, a sampling graph or a logits buffer
         self.sampling_on = False
         self.sampler = None
+        # penalties: the per-slot token statistics exist from the first penalised request on
+        self.penalties = None
         self._build_graphs()
         # rank 0 state
         self.incoming: "queue.Queue[Request]" = queue.Queue()
@@ -177,45 +179,70 @@ class PipelineServer:
             for mb in range(self.M):
                 if self.sampling_on:
                     from ..runtime.sampling import SamplingDecodeGraph
-                    g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
+                    g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S,
+                                            penalties=self.penalties)
                 else:
                     g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
                 self.graphs.append(g.capture())
         for st in self.streams:  # after weight loading and graph capture on the current stream
             st.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _enable_sampling(self) -> None:
+    def _enable_sampling(self, penalties: bool = False) -> None:
         """First non-greedy request (world == 1): build the Sampler and, in graph mode, replace
         every micro-batch's greedy graph by a SamplingDecodeGraph that takes over its device
         positions and tokens. Rows start greedy; a slot's parameters are written on admission.
         From here on greedy requests of this server take the arg-max of the bf16 logits in the
         decode graph (the first token still comes from the fused argmax)."""
-        from ..runtime.sampling import Sampler, SamplingDecodeGraph
-        self.sampler = Sampler(self.eng)
+        from ..runtime.sampling import PenaltyState, Sampler
+        if penalties:  # the first non-greedy request is a penalised one: one rebuild for both
+            self.penalties = PenaltyState(self.eng, self.B * self.M)
+        self.sampler = Sampler(self.eng, self.penalties)
         self.sampling_on = True
+        self._swap_sampling_graphs()
+
+    def _enable_penalties(self) -> None:
+        """First penalised request (sampling already on): allocate the PenaltyState and, in graph
+        mode, replace every sampling graph by one whose step runs ``lsa_penalize`` in front of
+        ``lsa_sample``, carrying positions, tokens and the rows' parameters over. Until then no
+        graph holds the penalty kernel and no table is allocated."""
+        from ..runtime.sampling import PenaltyState
+        self.penalties = PenaltyState(self.eng, self.B * self.M)
+        self.sampler.penalties = self.penalties
+        self._swap_sampling_graphs()
+
+    def _swap_sampling_graphs(self) -> None:
+        from ..runtime.sampling import SamplingDecodeGraph
         if not self.graph_mode:
             return
         torch.cuda.synchronize(self.device)
         old, self.graphs = self.graphs, []
         for mb in range(self.M):
-            g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S)
+            g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S,
+                                    penalties=self.penalties)
             g.pos.copy_(old[mb].pos)
             g.tokens.copy_(old[mb].tokens)
+            for i, p in enumerate(getattr(old[mb], "params", ())):
+                g.set_params(i, p)
             self.graphs.append(g.capture())
         del old
         for st in self.streams:
             st.wait_stream(torch.cuda.current_stream(self.device))
         torch.cuda.synchronize(self.device)
 
-    def _sample_rows(self, h, rows_idx, slots, positions, tok: torch.Tensor) -> torch.Tensor:
+    def _sample_rows(self, h, rows_idx, slots, positions, tok: torch.Tensor, tokens_in=None) -> torch.Tensor:
         """Replace the greedy tokens ``tok`` of the rows whose request samples: row
         ``rows_idx[i]`` of ``h`` belongs to ``slots[i]`` and its new token will sit at
-        ``positions[i]``."""
+        ``positions[i]``. ``tokens_in[i]``: the token the row was fed (a decode step), counted
+        by the penalties; None after a prefill."""
         reqs = [self.by_slot.get(s) for s in slots]
         sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
         if sel:
+            pen = {}
+            if self.penalties is not None:
+                pen = {"slots": [slots[i] for i in sel],
+                       "tokens_in": None if tokens_in is None else [tokens_in[i] for i in sel]}
             t = self.sampler.sample(h, [rows_idx[i] for i in sel], [reqs[i].sampling for i in sel],
-                                    [positions[i] for i in sel])
+                                    [positions[i] for i in sel], **pen)
             tok[torch.tensor(sel, dtype=torch.long, device=tok.device)] = t.to(tok.dtype)
         return tok
 
@@ -233,8 +260,13 @@ class PipelineServer:
             self.eng = self._build_engine(start, end)
             self.start, self.end = start, end
             if self.sampling_on:
-                from ..runtime.sampling import Sampler
-                self.sampler = Sampler(self.eng)
+                from ..runtime.sampling import PenaltyState, Sampler
+                if self.penalties is not None:  # drained: no request holds statistics
+                    self.penalties = None
+                    if self.gpu:
+                        torch.cuda.empty_cache()
+                    self.penalties = PenaltyState(self.eng, self.B * self.M)
+                self.sampler = Sampler(self.eng, self.penalties)
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
@@ -361,6 +393,11 @@ class PipelineServer:
                 tok = eng.head(h, emit_rows).to(torch.int32)
                 if self.sampling_on:
                     em = [it for it in items if it[3]]
+                    if self.penalties is not None:  # a penalised request enters its slot
+                        for (s, _, _, _) in em:
+                            r = self.by_slot.get(s)
+                            if r is not None and r.sampling is not None and r.sampling.penalized:
+                                self.penalties.admit(s, r.input_ids)
                     tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok)
                     if self.graph_mode:  # the slot's parameters, before its first decode step
                         for (s, _, _, _) in em:
@@ -403,7 +440,7 @@ class PipelineServer:
             if self.last:
                 tok = eng.head(h).to(torch.int32)
                 if self.sampling_on:
-                    tok = self._sample_rows(h, list(range(n)), slots, [p + 1 for p in pos], tok)
+                    tok = self._sample_rows(h, list(range(n)), slots, [p + 1 for p in pos], tok, tokens_in=ids)
                 if self.world == 1:
                     return self._to_host(tok)
                 self._send(tok.contiguous(), 0)
@@ -416,15 +453,16 @@ class PipelineServer:
     def submit(self, input_ids, max_new_tokens: int = 64, eos_ids=None, on_token=None,
                reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> int:
         """Queue a request (thread-safe). ``input_ids``: list of token ids. ``sampling``:
-        temperature / top-k / top-p / seed of the request (None or temperature 0: greedy); its
-        output depends only on its own prompt and seed, not on the slot or batch it runs in."""
+        temperature / top-k / top-p / seed and repetition / presence / frequency penalties of the
+        request (None, or temperature 0 with every penalty off: greedy); its output depends only
+        on its own prompt, seed and penalties, not on the slot or batch it runs in."""
         if not self.first:
             raise RuntimeError("requests are submitted on rank 0 (the ingress stage)")
-        if sampling is not None and sampling.greedy:
+        if sampling is not None and sampling.plain:
             sampling = None
         if sampling is not None and self.world > 1:
-            raise ValueError("sampling (temperature > 0) needs a single-stage server: with more than one pipeline "
-                             "stage only greedy requests are served")
+            raise ValueError("sampling (temperature > 0 or a penalty) needs a single-stage server: with more than one "
+                             "pipeline stage only greedy requests are served")
         ids = [int(x) for x in input_ids]
         if not ids:
             raise ValueError("empty prompt")
@@ -536,7 +574,9 @@ class PipelineServer:
                 break
             r = self.waiting.pop(0)
             if r.sampling is not None and not self.sampling_on:
-                self._enable_sampling()
+                self._enable_sampling(penalties=r.sampling.penalized)
+            if r.sampling is not None and r.sampling.penalized and self.penalties is None:
+                self._enable_penalties()
             r.slot, r.state, r.prefilled = s, PREFILLING, 0
             self.by_slot[s] = r
             if s in resets:

@@ -11,6 +11,9 @@ path that exists only when a request asks for it.
   ``lsa_sample`` -> ``argmax_finalize`` instead of the fused argmax, with per-row parameters on
   the device (:meth:`SamplingDecodeGraph.set_params` between replays).
 * :class:`EagerSamplingDecode` - the same interface for CPU engines.
+* :class:`PenaltyState` - the per-slot token statistics of the repetition / presence / frequency
+  penalties (``ops.penalties``); it exists only once a request asks for a penalty, and a graph or
+  Sampler built without it runs exactly the code above.
 
 A request's tokens depend only on its own logits, seed and positions (the noise is a pure
 function of seed, position and vocabulary index), not on the row, slot or batch it runs in.
@@ -23,6 +26,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from ..ops import penalties as P
 from ..ops import sampling as S
 from .engine import DecodeGraph, EagerDecode, StageEngine
 
@@ -31,11 +35,17 @@ from .engine import DecodeGraph, EagerDecode, StageEngine
 class SamplingParams:
     """``temperature == 0`` is greedy (the filters are then ignored). ``top_k == 0`` and
     ``top_p == 1`` switch the filters off. ``seed=None`` draws 64 bits from ``os.urandom`` and
-    stores them, so any run can be replayed from ``params.seed``."""
+    stores them, so any run can be replayed from ``params.seed``. ``repetition_penalty`` (HF's,
+    over prompt + generated tokens; 1 = off), ``presence_penalty`` and ``frequency_penalty``
+    (OpenAI / vLLM's, over generated tokens; 0 = off) edit the logits before the filters and the
+    draw - also at temperature 0, which then takes the arg-max of the penalised logits."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
     seed: Optional[int] = None
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
     def __post_init__(self):
         self.temperature, self.top_k, self.top_p = float(self.temperature), int(self.top_k), float(self.top_p)
@@ -50,16 +60,32 @@ class SamplingParams:
         self.seed = int(self.seed)
         if not 0 <= self.seed < 1 << 64:
             raise ValueError(f"seed must be a 64-bit unsigned value, got {self.seed}")
+        self.repetition_penalty = float(self.repetition_penalty)
+        self.presence_penalty, self.frequency_penalty = float(self.presence_penalty), float(self.frequency_penalty)
+        if not 0.0 < self.repetition_penalty < float("inf"):
+            raise ValueError(f"repetition_penalty must be a finite value > 0 (1 = off), got {self.repetition_penalty}")
+        for k in ("presence_penalty", "frequency_penalty"):
+            if not abs(getattr(self, k)) < float("inf"):
+                raise ValueError(f"{k} must be finite (0 = off), got {getattr(self, k)}")
 
     @property
     def greedy(self) -> bool:
         return self.temperature == 0.0
 
+    @property
+    def penalized(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def plain(self) -> bool:
+        """Needs no sampling path at all: temperature 0 and every penalty off."""
+        return self.greedy and not self.penalized
+
     @classmethod
     def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
-        """``temperature / top_k / top_p / seed`` keys of a request dict; None (greedy) when
-        none of them is present."""
-        keys = ("temperature", "top_k", "top_p", "seed")
+        """``temperature / top_k / top_p / seed / repetition_penalty / presence_penalty /
+        frequency_penalty`` keys of a request dict; None (greedy) when none of them is present."""
+        keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty")
         if not any(d.get(k) is not None for k in keys):
             return None
         return cls(**{k: d[k] for k in keys if d.get(k) is not None})
@@ -76,12 +102,64 @@ def _check_full_head(eng: StageEngine) -> None:
                                   f"rows [{eng.head_v0}, {eng.head_v1}) of {eng.cfg.head_rows} (split head)")
 
 
-class Sampler:
-    """Logits and sampled tokens of a stage that holds the whole lm_head."""
+class PenaltyState:
+    """The token statistics of the penalties: ``uint16 [n_slots, head_rows]`` on the engine's
+    device (bit 15: the token occurs in the slot's prompt; bits 0..14: how often it has been
+    generated, saturating) - 32.8 MB at 512 slots x 32000. Built when the first penalised
+    request arrives, like the logits buffer. torch stores the table as int16 (same bits)."""
 
-    def __init__(self, eng: StageEngine):
+    def __init__(self, eng: StageEngine, n_slots: int):
+        _check_full_head(eng)
+        self.eng, self.n_slots = eng, int(n_slots)
+        self.state = torch.zeros((self.n_slots, eng.cfg.head_rows), dtype=torch.int16, device=eng.device)
+
+    def admit(self, slot: int, prompt_ids) -> None:
+        """A penalised request enters ``slot``: zero its row, set the prompt bits."""
+        if not 0 <= slot < self.n_slots:
+            raise ValueError(f"slot {slot} outside the penalty table of {self.n_slots}")
+        ids = torch.as_tensor([int(t) for t in prompt_ids], dtype=torch.long, device=self.state.device)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.eng.cfg.vocab_size):
+            raise ValueError("prompt token outside the vocabulary")
+        row = self.state[slot]
+        row.zero_()
+        row[ids] = -0x8000  # int16 pattern of bit 15
+
+    def counts(self, slot: int) -> torch.Tensor:
+        """Generated-token counts of ``slot`` (int32 [vocab_size], on the host)."""
+        return (self.state[slot, :self.eng.cfg.vocab_size].cpu().to(torch.int32) & P.COUNT_MAX)
+
+    def apply(self, logits: torch.Tensor, slots, tokens_in, params_list: Sequence["SamplingParams"]) -> torch.Tensor:
+        """Count ``tokens_in[i]`` (None: nothing) into ``slots[i]`` and penalise row i of bf16
+        ``logits`` [n, >= vocab_size] by ``params_list[i]``: ``lsa_penalize`` in place on the GPU,
+        the numpy reference on a CPU engine. Returns the penalised logits."""
+        n, V = logits.shape[0], self.eng.cfg.vocab_size
+        slots = [int(s) for s in slots]
+        if len(slots) != n or len(params_list) != n or (tokens_in is not None and len(tokens_in) != n):
+            raise ValueError(f"penalties: {n} rows, {len(slots)} slots, {len(params_list)} params")
+        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
+            raise ValueError(f"penalties: slots {slots} must be distinct and below {self.n_slots}")
+        rep, pres, freq = ([getattr(p, k) for p in params_list]
+                           for k in ("repetition_penalty", "presence_penalty", "frequency_penalty"))
+        if not self.eng.gpu:
+            out, st = P.penalize_reference(logits.to(torch.bfloat16), V, self.state, slots, tokens_in, rep, pres, freq)
+            self.state.copy_(torch.from_numpy(st.view("int16")))
+            return out
+        dev = self.eng.device
+        f32 = lambda x: torch.tensor(x, dtype=torch.float32, device=dev)  # noqa: E731
+        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
+        P.penalize(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin, self.state,
+                   f32(rep), f32(pres), f32(freq))
+        return logits
+
+
+class Sampler:
+    """Logits and sampled tokens of a stage that holds the whole lm_head. ``penalties``: the
+    stage's :class:`PenaltyState`, applied by :meth:`sample` to the rows given ``slots``."""
+
+    def __init__(self, eng: StageEngine, penalties: Optional[PenaltyState] = None):
         _check_full_head(eng)
         self.eng = eng
+        self.penalties = penalties
 
     # ------------------------------------------------------------------ logits
     def logits(self, h: torch.Tensor, rows_idx=None) -> torch.Tensor:
@@ -164,10 +242,19 @@ class Sampler:
             hip.argmax_finalize(keys[c0:c0 + c], c, out[c0:c0 + c])
         return out.long()
 
-    def sample(self, h: torch.Tensor, rows_idx, params_list: Sequence[SamplingParams], positions) -> torch.Tensor:
+    def sample(self, h: torch.Tensor, rows_idx, params_list: Sequence[SamplingParams], positions,
+               slots=None, tokens_in=None) -> torch.Tensor:
         """Sampled tokens (int64 [n]) of the selected rows of the final hidden ``h``: the first
-        token after a prefill uses ``positions[i]`` = the prompt length."""
-        return self.sample_logits(self.logits(h, rows_idx), params_list, positions)
+        token after a prefill uses ``positions[i]`` = the prompt length. ``slots`` (with a
+        :class:`PenaltyState`): row i belongs to sequence slot ``slots[i]`` and is penalised by
+        its parameters first; ``tokens_in[i]`` is the token the row's step was fed (counted as
+        generated) - None for the first token after a prefill, which only sees the prompt."""
+        logits = self.logits(h, rows_idx)
+        if any(p.penalized for p in params_list):
+            if self.penalties is None or slots is None:
+                raise RuntimeError("a penalised request needs a PenaltyState (Sampler(eng, penalties=...)) and slots=")
+            logits = self.penalties.apply(logits, slots, tokens_in, params_list)
+        return self.sample_logits(logits, params_list, positions)
 
 
 def device_params(params_list: Sequence[SamplingParams], device) -> dict:
@@ -187,28 +274,60 @@ class SamplingDecodeGraph(DecodeGraph):
     parameters between replays. The row's Philox counter is its device position + 1 - the
     position the sampled token will occupy - so no host work happens per token.
 
+    With ``penalties`` (a :class:`PenaltyState` that covers this graph's slots) the step is logits
+    -> ``lsa_penalize`` -> ``lsa_sample``: the kernel counts the step's input tokens
+    (``self.tokens``) into the rows' slots and edits the logits by the per-row ``rep / pres / freq``
+    device arrays; rows whose penalties are off are skipped. Without it the captured step is
+    exactly the one above. ``debug_raw`` keeps a captured copy of the unpenalised logits in
+    ``raw_logits``.
+
     The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
-                 history_len: int = 0, scratch: int = 0):
+                 history_len: int = 0, scratch: int = 0, penalties: Optional[PenaltyState] = None,
+                 debug_raw: bool = False):
         if mode not in ("full", "last"):
             raise ValueError("SamplingDecodeGraph runs the head: mode 'full' or 'last'")
-        self.sampler = Sampler(eng)
+        self.sampler = Sampler(eng, penalties)
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len, scratch=scratch)
         dev = eng.device
         self.params = [GREEDY] * rows
         for k, v in device_params(self.params, dev).items():
             setattr(self, k, v)
         self.logits = torch.zeros((rows, eng.cfg.head_rows), dtype=torch.bfloat16, device=dev)
+        self.penalties = penalties
+        self.raw_logits = torch.zeros_like(self.logits) if debug_raw else None
+        if penalties is not None:
+            if penalties.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= penalties.n_slots:
+                raise ValueError("penalties: a PenaltyState of this engine with a distinct row per graph slot")
+            self.rep = torch.ones(rows, dtype=torch.float32, device=dev)
+            self.pres = torch.zeros(rows, dtype=torch.float32, device=dev)
+            self.freq = torch.zeros(rows, dtype=torch.float32, device=dev)
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
         """Small host-to-device copies on the current stream (like ``set_positions``)."""
         p = GREEDY if params is None else params
+        if p.penalized and self.penalties is None:
+            raise RuntimeError("a penalised request needs SamplingDecodeGraph(..., penalties=PenaltyState)")
         self.params[row] = p
         self.temperature[row] = p.temperature
         self.top_k[row] = p.top_k
         self.top_p[row] = p.top_p
         self.seed[row] = S.seed_to_i64(p.seed)
+        if self.penalties is not None:
+            self.rep[row] = p.repetition_penalty
+            self.pres[row] = p.presence_penalty
+            self.freq[row] = p.frequency_penalty
+
+    def capture(self, warmup: bool = True) -> "SamplingDecodeGraph":
+        """The warm-up run counts tokens into the penalty state: the graph's rows are restored."""
+        if self.penalties is None:
+            return super().capture(warmup)
+        idx = self.slot.long()
+        saved = self.penalties.state.index_select(0, idx)
+        super().capture(warmup)
+        self.penalties.state.index_copy_(0, idx, saved)
+        return self
 
     def _step(self) -> None:
         hip, eng, rows = self._hip, self.eng, self.rows
@@ -219,6 +338,11 @@ class SamplingDecodeGraph(DecodeGraph):
             h.copy_(self.h_in)
         eng._forward_hip(h, self.slot, self.pos, None, rows, nsplit=eng.decode_nsplit(rows))
         self.sampler.logits_into(h, rows, self.logits)
+        if self.raw_logits is not None:
+            self.raw_logits.copy_(self.logits)
+        if self.penalties is not None:
+            P.penalize(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.penalties.state,
+                       self.rep, self.pres, self.freq)
         S.sample(self.logits, eng.cfg.vocab_size, rows, self.temperature, self.top_k, self.top_p, self.seed, self.pos,
                  self.keys, ctr_add=1)
         hip.argmax_finalize(self.keys, rows, self.tokens, self.pos, 1, self.history,
@@ -228,11 +352,13 @@ class SamplingDecodeGraph(DecodeGraph):
 class EagerSamplingDecode(EagerDecode):
     """:class:`SamplingDecodeGraph`'s interface on devices without graphs (CPU engines)."""
 
-    def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0):
+    def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0,
+                 penalties: Optional[PenaltyState] = None):
         if mode not in ("full", "last"):
             raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
-        self.sampler = Sampler(eng)
+        self.sampler = Sampler(eng, penalties)
+        self.penalties = penalties
         self.params = [GREEDY] * rows
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
@@ -244,7 +370,8 @@ class EagerSamplingDecode(EagerDecode):
         slot, pos = eng.prefill_rows(self.slots, [1] * self.rows)
         h = eng.forward(h, slot, pos)
         eng.advance(self.slots, [1] * self.rows)
-        tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos])
+        pen = {} if self.penalties is None else {"slots": self.slots, "tokens_in": self.tokens.tolist()}
+        tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], **pen)
         self.tokens.copy_(tok.to(torch.int32))
         if self.history is not None and self.step < self.history.shape[0]:
             self.history[self.step] = self.tokens
@@ -254,4 +381,5 @@ class EagerSamplingDecode(EagerDecode):
     replay = _body
 
 
-__all__ = ["SamplingParams", "GREEDY", "Sampler", "SamplingDecodeGraph", "EagerSamplingDecode", "device_params"]
+__all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "SamplingDecodeGraph", "EagerSamplingDecode",
+           "device_params"]

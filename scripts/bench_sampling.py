@@ -9,7 +9,15 @@
    ``DecodeGraph`` of the same engine, at 1 and 512 rows: both graphs replayed in alternation over
    the same positions, device events around each window, median of the rounds.
 
+3. ``--penalties`` (results: profiles/penalties.md) instead: ``lsa_penalize`` alone at 1 and 512
+   rows of V = 32000 with about 200 non-zero states per row (rho 1.1, beta 0.2, an input token per
+   row) next to ``lsa_sample`` (top-p 0.9) on the same shapes: back-to-back launches and 50
+   launches captured in one graph (without the host's launch rate), with the bytes the kernel
+   reads (2 x 2 x V per row) and the GB/s they make; and the TPOT of a 7B-shaped ``SamplingDecodeGraph``
+   with penalties (temperature 0.7, top-p 0.9, rho 1.1, beta 0.2) against the same graph without.
+
     python scripts/bench_sampling.py [--layers 32] [--skip-kernel] [--skip-tpot] [--json-out FILE]
+    python scripts/bench_sampling.py --penalties [--layers 32] [--json-out FILE]
 """
 import argparse
 import json
@@ -21,9 +29,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llm_sharding_amd.config import LlamaConfig  # noqa: E402
+from llm_sharding_amd.ops import penalties as P  # noqa: E402
 from llm_sharding_amd.ops import sampling as S  # noqa: E402
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, StageEngine  # noqa: E402
-from llm_sharding_amd.runtime.sampling import SamplingDecodeGraph, SamplingParams  # noqa: E402
+from llm_sharding_amd.runtime.sampling import PenaltyState, SamplingDecodeGraph, SamplingParams  # noqa: E402
 
 DEV = "cuda"
 
@@ -39,7 +48,21 @@ def _events(fn, iters: int) -> float:
     return a.elapsed_time(b) / iters
 
 
-def bench_kernel(rows: int, V: int, mode: str, iters: int = 200) -> dict:
+def _graph_events(fn, iters: int) -> float:
+    """Milliseconds per call of ``fn`` with ``iters`` calls captured in one hipGraph: the host's
+    launch rate (about 16 us per call through ctypes) is out of the figure."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(iters):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    return _events(g.replay, 3) / iters
+
+
+def bench_kernel(rows: int, V: int, mode: str, iters: int = 200, graphed: bool = False) -> dict:
     g = torch.Generator(device=DEV).manual_seed(rows + V)
     lg = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
     T = torch.full((rows,), 0.7, dtype=torch.float32, device=DEV)
@@ -56,7 +79,10 @@ def bench_kernel(rows: int, V: int, mode: str, iters: int = 200) -> dict:
         run()
     torch.cuda.synchronize()
     ms = statistics.median(_events(run, iters) for _ in range(5))
-    return {"rows": rows, "V": V, "mode": mode, "us": round(ms * 1e3, 2), "pass_MB": round(rows * V * 2 / 1e6, 2)}
+    out = {"rows": rows, "V": V, "mode": mode, "us": round(ms * 1e3, 2), "pass_MB": round(rows * V * 2 / 1e6, 2)}
+    if graphed:
+        out["graphed_us"] = round(1e3 * _graph_events(run, 50), 2)
+    return out
 
 
 def bench_tpot(layers: int, rows: int, rounds: int = 5, steps: int = 20) -> dict:
@@ -110,23 +136,117 @@ def bench_tpot(layers: int, rows: int, rounds: int = 5, steps: int = 20) -> dict
             "sampling_spread_ms": round(max(times["sampling"]) - min(times["sampling"]), 4), **parts}
 
 
+def _sparse_state(n_slots: int, width: int, V: int, nonzero: int = 200) -> torch.Tensor:
+    """int16 [n_slots, width]: ``nonzero`` random columns per slot hold counts 1..5, half of them
+    the prompt bit too."""
+    g = torch.Generator().manual_seed(n_slots + V)
+    st = torch.zeros((n_slots, width), dtype=torch.int16)
+    for s in range(n_slots):
+        cols = torch.randperm(V, generator=g)[:nonzero]
+        val = torch.randint(1, 6, (nonzero,), generator=g).to(torch.int16)
+        val[::2] += -0x8000
+        st[s, cols] = val
+    return st.to(DEV)
+
+
+def bench_penalize(rows: int, V: int = 32000, iters: int = 200) -> dict:
+    g = torch.Generator(device=DEV).manual_seed(rows + V)
+    lg0 = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
+    lg = lg0.clone()
+    st0 = _sparse_state(rows, V, V)
+    st = st0.clone()
+    slot = torch.arange(rows, dtype=torch.int32, device=DEV)
+    tok = torch.randint(0, V, (rows,), generator=torch.Generator().manual_seed(3)).to(torch.int32).to(DEV)
+    rep = torch.full((rows,), 1.1, dtype=torch.float32, device=DEV)
+    pres = torch.zeros(rows, dtype=torch.float32, device=DEV)
+    freq = torch.full((rows,), 0.2, dtype=torch.float32, device=DEV)
+
+    def run():
+        P.penalize(lg, V, rows, slot, tok, st, rep, pres, freq)
+
+    for _ in range(10):
+        run()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(5):  # the same logits and counts in front of every window
+        lg.copy_(lg0)
+        st.copy_(st0)
+        ms.append(_events(run, iters))
+    us = statistics.median(ms) * 1e3
+    lg.copy_(lg0)
+    st.copy_(st0)
+    gus = 1e3 * _graph_events(run, 50)
+    read_mb = rows * V * 4 / 1e6
+    return {"kernel": "lsa_penalize", "rows": rows, "V": V, "us": round(us, 2), "graphed_us": round(gus, 2),
+            "read_MB": round(read_mb, 2), "graphed_GBps": round(read_mb / gus * 1e3, 1)}
+
+
+def bench_tpot_penalties(layers: int, rows: int, rounds: int = 5, steps: int = 20) -> dict:
+    cfg = LlamaConfig(num_hidden_layers=layers, vocab_size=32000, max_position_embeddings=512, name=f"7B-{layers}L")
+    eng = StageEngine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                      max_slots=rows, max_seq=128, max_prefill_rows=max(rows, 128))
+    pen = PenaltyState(eng, rows)
+    st0 = _sparse_state(rows, cfg.head_rows, cfg.vocab_size)
+    graphs = {"sampling": SamplingDecodeGraph(eng, rows, "full"),
+              "penalties": SamplingDecodeGraph(eng, rows, "full", penalties=pen)}
+    for r in range(rows):
+        graphs["sampling"].set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r))
+        graphs["penalties"].set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r, repetition_penalty=1.1,
+                                                         frequency_penalty=0.2))
+    for g in graphs.values():
+        g.capture()
+    tok0 = torch.randint(3, cfg.vocab_size, (rows,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(DEV)
+    times = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            g.set_positions()
+            g.tokens.copy_(tok0)
+            pen.state.copy_(st0)
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            times[name].append(_events(g.replay, steps))
+    ts, tp = statistics.median(times["sampling"]), statistics.median(times["penalties"])
+    del graphs, pen, eng
+    torch.cuda.empty_cache()
+    return {"layers": layers, "rows": rows, "sampling_ms": round(ts, 4), "penalties_ms": round(tp, 4),
+            "delta_ms": round(tp - ts, 4), "delta_pct": round(100 * (tp - ts) / ts, 2),
+            "sampling_spread_ms": round(max(times["sampling"]) - min(times["sampling"]), 4),
+            "penalties_spread_ms": round(max(times["penalties"]) - min(times["penalties"]), 4)}
+
+
+def main_penalties(a) -> dict:
+    out = {"kernel": [], "tpot": []}
+    for rows in (1, 512):
+        for r in (bench_penalize(rows), bench_kernel(rows, 32000, "top_p", graphed=True)):
+            out["kernel"].append(r)
+            print(json.dumps(r), flush=True)
+    if not a.skip_tpot:
+        for rows in (1, 512):
+            r = bench_tpot_penalties(a.layers, rows)
+            out["tpot"].append(r)
+            print(json.dumps(r), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--skip-tpot", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--penalties", action="store_true", help="measure lsa_penalize and the penalised step instead")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sampling.py measures on the GPU: none found")
-    out = {"kernel": [], "tpot": []}
-    for V in (() if a.skip_kernel else (32000, 128256)):
+    out = main_penalties(a) if a.penalties else {"kernel": [], "tpot": []}
+    for V in (() if a.skip_kernel or a.penalties else (32000, 128256)):
         for rows in (1, 128, 512):
             for mode in ("temperature", "top_k", "top_p"):
                 r = bench_kernel(rows, V, mode)
                 out["kernel"].append(r)
                 print(json.dumps(r), flush=True)
-    if not a.skip_tpot:
+    if not a.skip_tpot and not a.penalties:
         for rows in (1, 512):
             r = bench_tpot(a.layers, rows)
             out["tpot"].append(r)

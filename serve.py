@@ -21,8 +21,10 @@ finished request to stdout and, if ``reply_to`` is given, pushes ``{"request_id"
 "output_ids", "text", "ttft_ms", "tpot_ms"}`` back to that address. ``{"command":
 "shutdown"}`` drains the queue and stops every rank. Optional ``temperature``, ``top_k``,
 ``top_p`` and ``seed`` keys of a request sample on the device instead of greedy decode (one
-pipeline stage only); ``--temperature --top-k --top-p`` do the same for the synthetic load test
-(request i seeded with ``--seed`` + i).
+pipeline stage only), and ``repetition_penalty``, ``presence_penalty`` and ``frequency_penalty``
+keys penalise repeated tokens on the device (also at temperature 0; one stage only);
+``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty`` do
+the same for the synthetic load test (request i seeded with ``--seed`` + i).
 """
 import argparse
 import json
@@ -63,6 +65,10 @@ def main():
                                                                    "(request i uses seed --seed + i; one stage only)")
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="load test: HF's repetition_penalty "
+                                                                          "(1: off; one stage only)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0)
+    ap.add_argument("--frequency-penalty", type=float, default=0.0)
     a = ap.parse_args()
     if a.random:
         a.model = a.random
@@ -117,10 +123,11 @@ def main():
         g = torch.Generator().manual_seed(rc.seed + 1)
         for i in range(a.requests):
             ids = torch.randint(3, cfg.vocab_size, (a.prompt_len,), generator=g).tolist()
-            if a.temperature > 0:
+            pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
+            if a.temperature > 0 or pen != (1.0, 0.0, 0.0):
                 from llm_sharding_amd.runtime.sampling import SamplingParams
                 srv.submit(ids, rc.max_new_tokens, eos_ids=(),
-                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i))
+                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i, *pen))
             else:
                 srv.submit(ids, rc.max_new_tokens, eos_ids=())
         t0 = time.perf_counter()
