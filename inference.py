@@ -7,12 +7,17 @@ the seed in use is printed, and the same seed gives the same tokens.
 ``--repetition-penalty R`` (the reference's commented-out ``repetition_penalty=1.2``),
 ``--presence-penalty A`` and ``--frequency-penalty B`` penalise repeated tokens on the device, with
 or without a temperature (temperature 0: the arg-max of the penalised logits).
+``--logprobs N`` (0..20) prints each generated token's log-probability, rank and N most likely
+alternatives (of the penalised logits at temperature 1, before top-k / top-p); ``--score`` prints the
+prompt's own per-token log-probabilities, mean NLL and perplexity instead of generating.
 
     python inference.py --shards DIR [--prompt "..."] [--max-new-tokens 128]
     python inference.py --random llama2-7b --max-new-tokens 64     # random-init weights
     python inference.py --shards DIR --hf-compare HF_DIR           # + the reference's own path
     python inference.py --shards DIR --temperature 0.7 --top-p 0.9 --seed 1
     python inference.py --random llama2-7b --repetition-penalty 1.2
+    python inference.py --shards DIR --logprobs 5
+    python inference.py --shards DIR --score --prompt "..."
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
 (/root/reference/inference.py:16-45: transformers' AutoModelForCausalLM + greedy generate) on the
@@ -51,16 +56,22 @@ def build_parser() -> argparse.ArgumentParser:
                     help="subtracted from the logit of every token generated so far (0: off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0,
                     help="subtracted once per time a token has been generated (0: off)")
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N",
+                    help="print each generated token's log-probability, rank and N (0..20) alternatives")
+    ap.add_argument("--score", action="store_true",
+                    help="score the prompt instead of generating: per-token log-probabilities, mean NLL, perplexity")
     return ap
 
 
 def sampling_from_args(a):
-    """The run's SamplingParams; None for the greedy default (temperature 0, no penalty)."""
+    """The run's SamplingParams; None for the greedy default (temperature 0, no penalty, no
+    logprobs)."""
     from llm_sharding_amd.runtime.sampling import SamplingParams
     pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
-    if a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0):
+    if (a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0)
+            and a.logprobs is None):
         return None
-    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen)
+    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen, logprobs=a.logprobs)
     return None if sp.plain else sp
 
 
@@ -81,12 +92,18 @@ def main(argv=None):
                       max_seq=min(cfg.max_position_embeddings, 4096))
     ids = tok(a.prompt, return_tensors="pt")["input_ids"][0]
     print(f"[INFO] loaded in {time.perf_counter() - t0:.1f}s; prompt tokens {ids.numel()}")
+    if a.score:
+        return score(eng, tok, ids.tolist())
     slot, pos = eng.prefill_rows([0], [ids.numel()])
     h = eng.forward(eng.embed(ids.to(a.device)), slot, pos)
     eng.advance([0], [ids.numel()])
     if sp is not None:
-        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist())
-        return report(a, cfg, tok, ids, out, dt_s)
+        lp = {}
+        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist(), lp_out=lp)
+        out = report(a, cfg, tok, ids, out, dt_s)
+        if lp:
+            print_logprobs(tok, out, lp)
+        return out
     first = eng.head(h, [ids.numel() - 1])
     out = [int(first[0])]
     t1 = time.perf_counter()
@@ -110,11 +127,35 @@ def main(argv=None):
     return report(a, cfg, tok, ids, out, dt_s)
 
 
-def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None) -> tuple:
+def score(eng, tok, ids: list):
+    """--score: log p(ids[t + 1] | ids[..t]) of the prompt, its mean NLL and perplexity. Returns
+    the per-token log-probabilities (a list of len(ids) - 1 floats)."""
+    import math
+    from llm_sharding_amd.runtime.sampling import score_prompt
+    res = score_prompt(eng, ids)
+    lps = res.tok_lp.tolist()
+    for t, lp, rk in zip(ids[1:], lps, res.tok_rank.tolist()):
+        print(f"  {t:>7d} {tok.decode([t])!r:<16} logprob {lp:10.4f}  rank {rk}")
+    nll = -sum(lps) / len(lps)
+    print(f"[INFO] scored {len(lps)} tokens: mean NLL {nll:.6f}  perplexity {math.exp(nll):.6f}")
+    return lps
+
+
+def print_logprobs(tok, out: list, lp: dict) -> None:
+    """--logprobs: one line per generated token."""
+    for i, t in enumerate(out):
+        alts = "  ".join(f"{j}:{v:.3f}" for j, v in lp["top"][i])
+        print(f"  {t:>7d} {tok.decode([t])!r:<16} logprob {lp['lp'][i]:10.4f}  rank {lp['rank'][i]}"
+              + (f"  top [{alts}]" if alts else ""))
+
+
+def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out=None) -> tuple:
     """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from ``Sampler.sample``, the rest from a captured
     ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
-    sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along."""
+    sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along. With
+    ``sp.logprobs`` the tokens' log-probabilities, ranks and alternatives go into the dict
+    ``lp_out`` (``lp``, ``rank``, ``top``: per token a list of (id, logprob))."""
     from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, PenaltyState, Sampler, SamplingDecodeGraph
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
     pen, kw = None, {}
@@ -124,7 +165,14 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None) -> tup
         pen = PenaltyState(eng, 1)
         pen.admit(0, prompt_ids)
         kw = {"penalties": pen}
-    first = Sampler(eng, pen).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if pen is not None else None)
+    want_lp = sp.logprobs is not None
+    first = Sampler(eng, pen).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if pen is not None else None,
+                                     return_logprobs=want_lp)
+    steps = []
+    if want_lp:
+        first, lp0 = first
+        steps.append((lp0.tok_rank[0].clone(), lp0.top_id[0].clone(), lp0.top_lp[0].clone()))
+        kw["logprobs"] = True
     t1 = time.perf_counter()
     g = (SamplingDecodeGraph if eng.gpu else EagerSamplingDecode)(eng, 1, "full", history_len=max(1, n_new - 1), **kw)
     g.set_params(0, sp)
@@ -132,9 +180,16 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None) -> tup
     g.capture()
     for _ in range(n_new - 1):
         g.replay()
+        if want_lp:  # device-side copies, no host wait per token
+            steps.append((g.lp.tok_rank[0].clone(), g.lp.top_id[0].clone(), g.lp.top_lp[0].clone()))
     if eng.gpu:
         torch.cuda.synchronize()
-    return [int(first[0])] + g.history[:n_new - 1, 0].tolist(), time.perf_counter() - t1
+    dt_s = time.perf_counter() - t1
+    if want_lp and lp_out is not None:
+        lp_out["lp"] = [float(lp0.tok_lp[0])] + g.lp_history[:n_new - 1, 0].tolist()
+        lp_out["rank"] = [int(r) for r, _, _ in steps]
+        lp_out["top"] = [list(zip(i[:sp.logprobs].tolist(), v[:sp.logprobs].tolist())) for _, i, v in steps]
+    return [int(first[0])] + g.history[:n_new - 1, 0].tolist(), dt_s
 
 
 def report(a, cfg, tok, ids, out, dt_s):

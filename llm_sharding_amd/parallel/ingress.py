@@ -18,7 +18,9 @@ from .transport import Again, PullSocket, PushSocket
 
 class Replies:
     """on_token callback: prints each finished request and pushes ``{"request_id",
-    "output_ids", "text", "ttft_ms", "tpot_ms"}`` to its ``reply_to`` address."""
+    "output_ids", "text", "ttft_ms", "tpot_ms"}`` to its ``reply_to`` address - plus a
+    ``"logprobs"`` dict (``token_logprobs``, ``ranks`` and, with ``logprobs >= 1``, ``top_logprobs``:
+    per token a list of ``[id, logprob]`` pairs) for a request that asked for them."""
 
     def __init__(self, tokenizer=None, verbose: bool = True, on_done: Optional[Callable] = None):
         self.tok = tokenizer
@@ -46,9 +48,13 @@ class Replies:
         if self.on_done is not None:
             self.on_done(r, text)
         if r.reply_to:
-            self._send(r.reply_to, protocol.encode({
-                "request_id": r.rid, "output_ids": list(r.output_ids), "text": text,
-                "ttft_ms": r.ttft_ms, "tpot_ms": r.tpot_ms}))
+            reply = {"request_id": r.rid, "output_ids": list(r.output_ids), "text": text,
+                     "ttft_ms": r.ttft_ms, "tpot_ms": r.tpot_ms}
+            if getattr(r, "token_logprobs", None) is not None:
+                reply["logprobs"] = {"token_logprobs": list(r.token_logprobs), "ranks": list(r.ranks)}
+                if r.top_logprobs is not None:
+                    reply["logprobs"]["top_logprobs"] = [[[int(i), float(v)] for i, v in t] for t in r.top_logprobs]
+            self._send(r.reply_to, protocol.encode(reply))
 
     def error(self, reply_to: Optional[str], reason: str, request_id=None) -> None:
         """Tell a client its request will not be served (``{"request_id", "error"}``)."""
@@ -78,8 +84,9 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     lists, else ``text`` through the tokenizer; optional ``temperature``, ``top_k``, ``top_p``,
     ``seed``: sampling instead of greedy decode, a batch's prompts each drawing their own seed
     when none is given; optional ``repetition_penalty``, ``presence_penalty``,
-    ``frequency_penalty``: penalties on repeated tokens, with or without a temperature). Returns
-    the number of requests queued."""
+    ``frequency_penalty``: penalties on repeated tokens, with or without a temperature; optional
+    ``logprobs`` (0..20): per-token log-probabilities, ranks and that many alternatives in the
+    reply). Returns the number of requests queued."""
     n_new = int(msg.get("max_new_tokens") or default_new)
     rows = msg.get("input_ids")
     if rows is None:
@@ -92,7 +99,7 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     n = 0
     for ids in rows:
         try:
-            # optional temperature / top_k / top_p / seed / *_penalty keys; absent: greedy (the plain call)
+            # optional temperature / top_k / top_p / seed / *_penalty / logprobs keys; absent: greedy (the plain call)
             sp = SamplingParams.from_dict(msg)
             kw = {} if sp is None else {"sampling": sp}
             srv.submit(ids, n_new, on_token=replies, reply_to=msg.get("reply_to"), **kw)

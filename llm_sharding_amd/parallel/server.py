@@ -60,6 +60,10 @@ class Request:
     on_token: Optional[Callable] = None
     reply_to: Optional[str] = None
     sampling: Optional[SamplingParams] = None  # None: greedy
+    # sampling.logprobs set: one entry per generated token (else they stay None)
+    token_logprobs: Optional[List[float]] = None
+    ranks: Optional[List[int]] = None
+    top_logprobs: Optional[List[list]] = None  # logprobs >= 1: [[id, logprob], ...] per token
     state: str = WAITING
     slot: int = -1
     prefilled: int = 0
@@ -144,6 +148,9 @@ class PipelineServer:
         self.sampler = None
         # penalties: the per-slot token statistics exist from the first penalised request on
         self.penalties = None
+        # logprobs: the graphs carry the lsa_logprobs launch from the first request that asks on
+        self.logprobs_on = False
+        self._lp_out: List = [None] * microbatches  # logprobs of a micro-batch's outstanding command
         self._build_graphs()
         # rank 0 state
         self.incoming: "queue.Queue[Request]" = queue.Queue()
@@ -180,14 +187,14 @@ class PipelineServer:
                 if self.sampling_on:
                     from ..runtime.sampling import SamplingDecodeGraph
                     g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S,
-                                            penalties=self.penalties)
+                                            penalties=self.penalties, logprobs=self.logprobs_on)
                 else:
                     g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
                 self.graphs.append(g.capture())
         for st in self.streams:  # after weight loading and graph capture on the current stream
             st.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _enable_sampling(self, penalties: bool = False) -> None:
+    def _enable_sampling(self, penalties: bool = False, logprobs: bool = False) -> None:
         """First non-greedy request (world == 1): build the Sampler and, in graph mode, replace
         every micro-batch's greedy graph by a SamplingDecodeGraph that takes over its device
         positions and tokens. Rows start greedy; a slot's parameters are written on admission.
@@ -196,6 +203,7 @@ class PipelineServer:
         from ..runtime.sampling import PenaltyState, Sampler
         if penalties:  # the first non-greedy request is a penalised one: one rebuild for both
             self.penalties = PenaltyState(self.eng, self.B * self.M)
+        self.logprobs_on = self.logprobs_on or logprobs
         self.sampler = Sampler(self.eng, self.penalties)
         self.sampling_on = True
         self._swap_sampling_graphs()
@@ -210,6 +218,14 @@ class PipelineServer:
         self.sampler.penalties = self.penalties
         self._swap_sampling_graphs()
 
+    def _enable_logprobs(self) -> None:
+        """First request with ``logprobs`` (sampling already on): in graph mode, replace every
+        sampling graph by one whose step ends in ``lsa_logprobs``, carrying positions, tokens and
+        the rows' parameters over. A server that never sees such a request runs the graphs
+        without that launch."""
+        self.logprobs_on = True
+        self._swap_sampling_graphs()
+
     def _swap_sampling_graphs(self) -> None:
         from ..runtime.sampling import SamplingDecodeGraph
         if not self.graph_mode:
@@ -218,7 +234,7 @@ class PipelineServer:
         old, self.graphs = self.graphs, []
         for mb in range(self.M):
             g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S,
-                                    penalties=self.penalties)
+                                    penalties=self.penalties, logprobs=self.logprobs_on)
             g.pos.copy_(old[mb].pos)
             g.tokens.copy_(old[mb].tokens)
             for i, p in enumerate(getattr(old[mb], "params", ())):
@@ -229,11 +245,13 @@ class PipelineServer:
             st.wait_stream(torch.cuda.current_stream(self.device))
         torch.cuda.synchronize(self.device)
 
-    def _sample_rows(self, h, rows_idx, slots, positions, tok: torch.Tensor, tokens_in=None) -> torch.Tensor:
+    def _sample_rows(self, h, rows_idx, slots, positions, tok: torch.Tensor, tokens_in=None,
+                     mb: int = 0) -> torch.Tensor:
         """Replace the greedy tokens ``tok`` of the rows whose request samples: row
         ``rows_idx[i]`` of ``h`` belongs to ``slots[i]`` and its new token will sit at
         ``positions[i]``. ``tokens_in[i]``: the token the row was fed (a decode step), counted
-        by the penalties; None after a prefill."""
+        by the penalties; None after a prefill. With logprobs on, the log-probabilities of the
+        rows that ask for them wait in ``_lp_out[mb]`` for the command's collection."""
         reqs = [self.by_slot.get(s) for s in slots]
         sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
         if sel:
@@ -241,10 +259,42 @@ class PipelineServer:
             if self.penalties is not None:
                 pen = {"slots": [slots[i] for i in sel],
                        "tokens_in": None if tokens_in is None else [tokens_in[i] for i in sel]}
+            want_lp = self.logprobs_on and any(reqs[i].sampling.logprobs is not None for i in sel)
             t = self.sampler.sample(h, [rows_idx[i] for i in sel], [reqs[i].sampling for i in sel],
-                                    [positions[i] for i in sel], **pen)
+                                    [positions[i] for i in sel], return_logprobs=want_lp, **pen)
+            if want_lp:
+                t, lp = t
+                self._lp_out[mb] = ([slots[i] for i in sel], self._lp_to_host(lp))
             tok[torch.tensor(sel, dtype=torch.long, device=tok.device)] = t.to(tok.dtype)
         return tok
+
+    def _lp_to_host(self, lp):
+        """(tok_lp, tok_rank, top_id, top_lp) on their way to the host, like :meth:`_to_host`."""
+        return [self._to_host(t) for t in (lp.tok_lp, lp.tok_rank, lp.top_id, lp.top_lp)]
+
+    def _take_logprobs(self, mb: int) -> dict:
+        """The logprobs the micro-batch's collected command left: slot -> (lp, rank, ids, lps)."""
+        o, self._lp_out[mb] = self._lp_out[mb], None
+        if o is None:
+            return {}
+        slots, parts = o
+        lp, rank, ids, lps = (self._host_list(p) for p in parts)
+        return {s: (lp[i], rank[i], ids[i], lps[i]) for i, s in enumerate(slots)}
+
+    @staticmethod
+    def _record_logprobs(r: Request, entry) -> None:
+        """Append one generated token's logprobs to a request that asked for them."""
+        if r.sampling is None or r.sampling.logprobs is None or entry is None:
+            return
+        lp, rank, ids, lps = entry
+        if r.token_logprobs is None:
+            r.token_logprobs, r.ranks = [], []
+            r.top_logprobs = [] if r.sampling.logprobs > 0 else None
+        r.token_logprobs.append(float(lp))
+        r.ranks.append(int(rank))
+        if r.top_logprobs is not None:
+            n = r.sampling.logprobs
+            r.top_logprobs.append([[int(i), float(v)] for i, v in zip(ids[:n], lps[:n]) if i >= 0])
 
     def _reshard(self, start: int, end: int) -> None:
         """Every rank, pipeline drained: free this stage's engine, load layers [start, end),
@@ -398,7 +448,8 @@ class PipelineServer:
                             r = self.by_slot.get(s)
                             if r is not None and r.sampling is not None and r.sampling.penalized:
                                 self.penalties.admit(s, r.input_ids)
-                    tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok)
+                    tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok,
+                                            mb=mb)
                     if self.graph_mode:  # the slot's parameters, before its first decode step
                         for (s, _, _, _) in em:
                             r = self.by_slot.get(s)
@@ -417,6 +468,8 @@ class PipelineServer:
                 g.replay()
                 if self.last:
                     if self.world == 1:
+                        if self.logprobs_on and g.lp is not None:
+                            self._lp_out[mb] = (self._slots(mb), self._lp_to_host(g.lp))
                         return self._to_host(g.tokens)
                     out = g.tokens.clone()
                     self._send(out, 0)
@@ -440,7 +493,8 @@ class PipelineServer:
             if self.last:
                 tok = eng.head(h).to(torch.int32)
                 if self.sampling_on:
-                    tok = self._sample_rows(h, list(range(n)), slots, [p + 1 for p in pos], tok, tokens_in=ids)
+                    tok = self._sample_rows(h, list(range(n)), slots, [p + 1 for p in pos], tok, tokens_in=ids,
+                                            mb=mb)
                 if self.world == 1:
                     return self._to_host(tok)
                 self._send(tok.contiguous(), 0)
@@ -453,16 +507,18 @@ class PipelineServer:
     def submit(self, input_ids, max_new_tokens: int = 64, eos_ids=None, on_token=None,
                reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> int:
         """Queue a request (thread-safe). ``input_ids``: list of token ids. ``sampling``:
-        temperature / top-k / top-p / seed and repetition / presence / frequency penalties of the
-        request (None, or temperature 0 with every penalty off: greedy); its output depends only
-        on its own prompt, seed and penalties, not on the slot or batch it runs in."""
+        temperature / top-k / top-p / seed, repetition / presence / frequency penalties and
+        ``logprobs`` of the request (None, or temperature 0 with every penalty off and no logprobs:
+        greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
+        batch it runs in. With ``logprobs`` the finished :class:`Request` holds ``token_logprobs``,
+        ``ranks`` and (``logprobs >= 1``) ``top_logprobs``, one entry per generated token."""
         if not self.first:
             raise RuntimeError("requests are submitted on rank 0 (the ingress stage)")
         if sampling is not None and sampling.plain:
             sampling = None
         if sampling is not None and self.world > 1:
-            raise ValueError("sampling (temperature > 0 or a penalty) needs a single-stage server: with more than one "
-                             "pipeline stage only greedy requests are served")
+            raise ValueError("sampling (temperature > 0, a penalty or logprobs) needs a single-stage server: with more "
+                             "than one pipeline stage only greedy requests are served")
         ids = [int(x) for x in input_ids]
         if not ids:
             raise ValueError("empty prompt")
@@ -536,10 +592,12 @@ class PipelineServer:
             else:
                 toks = self._host_list(local)
             now = time.perf_counter()
+            lps = self._take_logprobs(mb)
             for r, t in zip(emitted, toks):
                 r.state = DECODING
                 if self.graph_mode:
                     self.graphs[mb].tokens[r.slot - mb * self.B] = t
+                self._record_logprobs(r, lps.get(r.slot))
                 self._emit(r, int(t), now)
         elif kind == CMD_DECODE:
             if local is None:
@@ -554,15 +612,18 @@ class PipelineServer:
             else:
                 toks = self._host_list(local)
             now = time.perf_counter()
+            lps = self._take_logprobs(mb)
             if self.graph_mode:
                 for i, s in enumerate(self._slots(mb)):
                     r = self.by_slot.get(s)
                     if r is not None and r.state == DECODING and r.rid in info:
+                        self._record_logprobs(r, lps.get(s))
                         self._emit(r, int(toks[i]), now)
             else:
                 for (s, rid), t in zip(info, toks):
                     r = self.by_slot.get(s)
                     if r is not None and r.rid == rid:
+                        self._record_logprobs(r, lps.get(s))
                         self._emit(r, int(t), now)
 
     def _schedule(self, mb: int) -> bool:
@@ -574,9 +635,11 @@ class PipelineServer:
                 break
             r = self.waiting.pop(0)
             if r.sampling is not None and not self.sampling_on:
-                self._enable_sampling(penalties=r.sampling.penalized)
+                self._enable_sampling(penalties=r.sampling.penalized, logprobs=r.sampling.logprobs is not None)
             if r.sampling is not None and r.sampling.penalized and self.penalties is None:
                 self._enable_penalties()
+            if r.sampling is not None and r.sampling.logprobs is not None and not self.logprobs_on:
+                self._enable_logprobs()
             r.slot, r.state, r.prefilled = s, PREFILLING, 0
             self.by_slot[s] = r
             if s in resets:

@@ -14,18 +14,25 @@ path that exists only when a request asks for it.
 * :class:`PenaltyState` - the per-slot token statistics of the repetition / presence / frequency
   penalties (``ops.penalties``); it exists only once a request asks for a penalty, and a graph or
   Sampler built without it runs exactly the code above.
+* Log-probabilities (``SamplingParams.logprobs``, ``ops.logprobs``): :meth:`Sampler.logprobs`,
+  ``SamplingDecodeGraph(..., logprobs=True)`` (one ``lsa_logprobs`` launch behind
+  ``argmax_finalize``; a graph built without it captures exactly the step above) and
+  :func:`score_prompt`. The numbers describe the bf16 row ``lsa_sample`` reads: after the
+  penalties, before temperature and the top-k / top-p filters.
 
 A request's tokens depend only on its own logits, seed and positions (the noise is a pure
 function of seed, position and vocabulary index), not on the row, slot or batch it runs in.
 """
 from __future__ import annotations
 
+import numbers
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
 
+from ..ops import logprobs as LP
 from ..ops import penalties as P
 from ..ops import sampling as S
 from .engine import DecodeGraph, EagerDecode, StageEngine
@@ -38,7 +45,10 @@ class SamplingParams:
     stores them, so any run can be replayed from ``params.seed``. ``repetition_penalty`` (HF's,
     over prompt + generated tokens; 1 = off), ``presence_penalty`` and ``frequency_penalty``
     (OpenAI / vLLM's, over generated tokens; 0 = off) edit the logits before the filters and the
-    draw - also at temperature 0, which then takes the arg-max of the penalised logits."""
+    draw - also at temperature 0, which then takes the arg-max of the penalised logits.
+    ``logprobs`` (None = off): ``0`` returns the chosen token's log-probability and rank, ``1..20``
+    also that many most likely alternatives - of the penalised logits at temperature 1, before the
+    top-k / top-p filters."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
@@ -46,6 +56,7 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    logprobs: Optional[int] = None
 
     def __post_init__(self):
         self.temperature, self.top_k, self.top_p = float(self.temperature), int(self.top_k), float(self.top_p)
@@ -67,6 +78,11 @@ class SamplingParams:
         for k in ("presence_penalty", "frequency_penalty"):
             if not abs(getattr(self, k)) < float("inf"):
                 raise ValueError(f"{k} must be finite (0 = off), got {getattr(self, k)}")
+        if self.logprobs is not None:
+            lp = self.logprobs
+            if isinstance(lp, bool) or not isinstance(lp, numbers.Integral) or not 0 <= lp <= LP.TOP_MAX:
+                raise ValueError(f"logprobs must be None (off) or an integer in [0, {LP.TOP_MAX}], got {lp!r}")
+            self.logprobs = int(lp)
 
     @property
     def greedy(self) -> bool:
@@ -78,14 +94,21 @@ class SamplingParams:
 
     @property
     def plain(self) -> bool:
-        """Needs no sampling path at all: temperature 0 and every penalty off."""
-        return self.greedy and not self.penalized
+        """Needs no sampling path at all: temperature 0, every penalty off, no logprobs."""
+        return self.greedy and not self.penalized and self.logprobs is None
+
+    @property
+    def n_top(self) -> int:
+        """The row's ``n_top`` of ``lsa_logprobs``: -1 (skip the row) without ``logprobs``."""
+        return -1 if self.logprobs is None else self.logprobs
 
     @classmethod
     def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
         """``temperature / top_k / top_p / seed / repetition_penalty / presence_penalty /
-        frequency_penalty`` keys of a request dict; None (greedy) when none of them is present."""
-        keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty")
+        frequency_penalty / logprobs`` keys of a request dict; None (greedy) when none of them is
+        present."""
+        keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty",
+                "logprobs")
         if not any(d.get(k) is not None for k in keys):
             return None
         return cls(**{k: d[k] for k in keys if d.get(k) is not None})
@@ -242,19 +265,57 @@ class Sampler:
             hip.argmax_finalize(keys[c0:c0 + c], c, out[c0:c0 + c])
         return out.long()
 
+    def logprobs(self, logits: torch.Tensor, targets, n_top) -> LP.Logprobs:
+        """Log-probabilities of bf16 ``logits`` [n, >= vocab_size] (``ops.logprobs``' contract):
+        ``targets`` / ``n_top`` per row (or one value for all). ``lsa_logprobs`` on the GPU, the
+        fp64 reference on a CPU engine. Returns :class:`ops.logprobs.Logprobs` of torch tensors on
+        the logits' device: ``lse`` / ``tok_lp`` fp32 [n], ``tok_rank`` int32 [n], ``top_id`` int32
+        and ``top_lp`` fp32 [n, TOP_MAX]; rows with ``n_top = -1`` hold NaN / 0 / -1 / -inf."""
+        eng, V, n = self.eng, self.eng.cfg.vocab_size, logits.shape[0]
+
+        def per_row(x):
+            x = x.tolist() if isinstance(x, torch.Tensor) else x
+            x = [int(v) for v in x] if isinstance(x, (list, tuple)) else [int(x)] * n
+            if len(x) != n:
+                raise ValueError(f"logprobs: {len(x)} per-row values for {n} rows")
+            return x
+
+        targets, n_top = per_row(targets), per_row(n_top)
+        if any(k > LP.TOP_MAX for k in n_top):
+            raise ValueError(f"logprobs: n_top above {LP.TOP_MAX}")
+        if not eng.gpu:
+            ref = LP.logprobs_reference(logits.to(torch.bfloat16), V, n_top, targets)
+            return LP.Logprobs(torch.from_numpy(ref.lse).float(), torch.from_numpy(ref.tok_lp).float(),
+                               torch.from_numpy(ref.tok_rank).int(), torch.from_numpy(ref.top_id).int(),
+                               torch.from_numpy(ref.top_lp).float())
+        dev = eng.device
+        out = LP.alloc_outputs(n, dev)
+        nt = torch.tensor(n_top, dtype=torch.int32, device=dev)
+        tg = torch.tensor(targets, dtype=torch.int32, device=dev)
+        for c0 in range(0, n, 32768):
+            c = min(32768, n - c0)
+            LP.logprobs(logits[c0:c0 + c], V, c, nt[c0:c0 + c], tg[c0:c0 + c],
+                        LP.Logprobs(*(t[c0:c0 + c] for t in out)))
+        return out
+
     def sample(self, h: torch.Tensor, rows_idx, params_list: Sequence[SamplingParams], positions,
-               slots=None, tokens_in=None) -> torch.Tensor:
+               slots=None, tokens_in=None, return_logprobs: bool = False):
         """Sampled tokens (int64 [n]) of the selected rows of the final hidden ``h``: the first
         token after a prefill uses ``positions[i]`` = the prompt length. ``slots`` (with a
         :class:`PenaltyState`): row i belongs to sequence slot ``slots[i]`` and is penalised by
         its parameters first; ``tokens_in[i]`` is the token the row's step was fed (counted as
-        generated) - None for the first token after a prefill, which only sees the prompt."""
+        generated) - None for the first token after a prefill, which only sees the prompt.
+        ``return_logprobs``: returns ``(tokens, Logprobs)`` - the log-probabilities of the sampled
+        tokens under the (penalised) logits, for the rows whose parameters ask for them."""
         logits = self.logits(h, rows_idx)
         if any(p.penalized for p in params_list):
             if self.penalties is None or slots is None:
                 raise RuntimeError("a penalised request needs a PenaltyState (Sampler(eng, penalties=...)) and slots=")
             logits = self.penalties.apply(logits, slots, tokens_in, params_list)
-        return self.sample_logits(logits, params_list, positions)
+        tok = self.sample_logits(logits, params_list, positions)
+        if not return_logprobs:
+            return tok
+        return tok, self.logprobs(logits, tok, [p.n_top for p in params_list])
 
 
 def device_params(params_list: Sequence[SamplingParams], device) -> dict:
@@ -281,11 +342,17 @@ class SamplingDecodeGraph(DecodeGraph):
     exactly the one above. ``debug_raw`` keeps a captured copy of the unpenalised logits in
     ``raw_logits``.
 
+    With ``logprobs=True`` the step ends in one more launch, ``lsa_logprobs`` on the same logits
+    with the freshly written ``self.tokens`` as targets: the per-row ``n_top`` (-1 = the row is
+    skipped, written by :meth:`set_params`) and the outputs ``lp`` (:class:`ops.logprobs.Logprobs`)
+    live on the device; with a token history, ``lp_history`` keeps ``tok_lp`` of the same steps
+    (NaN where a row was skipped). Without it the captured step is exactly the one above.
+
     The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
                  history_len: int = 0, scratch: int = 0, penalties: Optional[PenaltyState] = None,
-                 debug_raw: bool = False):
+                 debug_raw: bool = False, logprobs: bool = False):
         if mode not in ("full", "last"):
             raise ValueError("SamplingDecodeGraph runs the head: mode 'full' or 'last'")
         self.sampler = Sampler(eng, penalties)
@@ -303,12 +370,20 @@ class SamplingDecodeGraph(DecodeGraph):
             self.rep = torch.ones(rows, dtype=torch.float32, device=dev)
             self.pres = torch.zeros(rows, dtype=torch.float32, device=dev)
             self.freq = torch.zeros(rows, dtype=torch.float32, device=dev)
+        self.lp = self.n_top = self.lp_history = None
+        if logprobs:
+            self.n_top = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+            self.lp = LP.alloc_outputs(rows, dev)
+            if self.history is not None:
+                self.lp_history = torch.full(self.history.shape, float("nan"), dtype=torch.float32, device=dev)
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
         """Small host-to-device copies on the current stream (like ``set_positions``)."""
         p = GREEDY if params is None else params
         if p.penalized and self.penalties is None:
             raise RuntimeError("a penalised request needs SamplingDecodeGraph(..., penalties=PenaltyState)")
+        if p.logprobs is not None and self.lp is None:
+            raise RuntimeError("a request with logprobs needs SamplingDecodeGraph(..., logprobs=True)")
         self.params[row] = p
         self.temperature[row] = p.temperature
         self.top_k[row] = p.top_k
@@ -318,15 +393,20 @@ class SamplingDecodeGraph(DecodeGraph):
             self.rep[row] = p.repetition_penalty
             self.pres[row] = p.presence_penalty
             self.freq[row] = p.frequency_penalty
+        if self.lp is not None:
+            self.n_top[row] = p.n_top
 
     def capture(self, warmup: bool = True) -> "SamplingDecodeGraph":
         """The warm-up run counts tokens into the penalty state: the graph's rows are restored."""
         if self.penalties is None:
-            return super().capture(warmup)
-        idx = self.slot.long()
-        saved = self.penalties.state.index_select(0, idx)
-        super().capture(warmup)
-        self.penalties.state.index_copy_(0, idx, saved)
+            super().capture(warmup)
+        else:
+            idx = self.slot.long()
+            saved = self.penalties.state.index_select(0, idx)
+            super().capture(warmup)
+            self.penalties.state.index_copy_(0, idx, saved)
+        if self.lp_history is not None:
+            self.lp_history.fill_(float("nan"))
         return self
 
     def _step(self) -> None:
@@ -347,22 +427,33 @@ class SamplingDecodeGraph(DecodeGraph):
                  self.keys, ctr_add=1)
         hip.argmax_finalize(self.keys, rows, self.tokens, self.pos, 1, self.history,
                             self.step_ctr if self.history is not None else None)
+        if self.lp is not None:
+            LP.logprobs(self.logits, eng.cfg.vocab_size, rows, self.n_top, self.tokens, self.lp,
+                        lp_history=self.lp_history, step_ctr=self.step_ctr if self.lp_history is not None else None)
 
 
 class EagerSamplingDecode(EagerDecode):
     """:class:`SamplingDecodeGraph`'s interface on devices without graphs (CPU engines)."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0,
-                 penalties: Optional[PenaltyState] = None):
+                 penalties: Optional[PenaltyState] = None, logprobs: bool = False):
         if mode not in ("full", "last"):
             raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
         self.sampler = Sampler(eng, penalties)
         self.penalties = penalties
         self.params = [GREEDY] * rows
+        self.lp = self.lp_history = None
+        if logprobs:
+            self.lp = self.sampler.logprobs(torch.zeros((rows, eng.cfg.head_rows), dtype=torch.bfloat16), 0, -1)
+            if self.history is not None:
+                self.lp_history = torch.full(self.history.shape, float("nan"), dtype=torch.float32)
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
-        self.params[row] = GREEDY if params is None else params
+        p = GREEDY if params is None else params
+        if p.logprobs is not None and self.lp is None:
+            raise RuntimeError("a request with logprobs needs EagerSamplingDecode(..., logprobs=True)")
+        self.params[row] = p
 
     def _body(self) -> None:
         eng = self.eng
@@ -371,15 +462,59 @@ class EagerSamplingDecode(EagerDecode):
         h = eng.forward(h, slot, pos)
         eng.advance(self.slots, [1] * self.rows)
         pen = {} if self.penalties is None else {"slots": self.slots, "tokens_in": self.tokens.tolist()}
-        tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], **pen)
+        tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], return_logprobs=self.lp is not None,
+                                  **pen)
+        if self.lp is not None:
+            tok, self.lp = tok
         self.tokens.copy_(tok.to(torch.int32))
         if self.history is not None and self.step < self.history.shape[0]:
             self.history[self.step] = self.tokens
+            if self.lp_history is not None:
+                self.lp_history[self.step] = self.lp.tok_lp
         self.step += 1
         self._out = h
 
     replay = _body
 
 
+SCORE_CHUNK_BYTES = 64 << 20  # score_prompt: no more logits than this exist at once
+
+
+def score_prompt(eng: StageEngine, ids, top: int = 0, slot: int = 0):
+    """Teacher-forced log-probabilities of a prompt: prefills ``ids`` into KV slot ``slot`` (from
+    position 0) and returns :class:`ops.logprobs.Logprobs` of host tensors with ``len(ids) - 1``
+    rows - ``tok_lp[t] = log p(ids[t + 1] | ids[..t])`` (fp32), ``tok_rank``, and the ``top``
+    (0..20) most likely tokens per position in ``top_id`` / ``top_lp``. The logits are produced and
+    reduced in chunks of at most 64 MiB; GPU and CPU engines, bf16 and fp8 heads; needs the whole
+    model's head on this engine (NotImplementedError on a split head)."""
+    sampler = Sampler(eng)
+    if not eng.has_embed:
+        raise RuntimeError("[ERROR] score_prompt needs the stage that owns the embedding")
+    ids = [int(t) for t in ids]
+    top = int(top)
+    if len(ids) < 2:
+        raise ValueError("score_prompt needs at least two tokens")
+    if not 0 <= top <= LP.TOP_MAX:
+        raise ValueError(f"top must be in [0, {LP.TOP_MAX}], got {top}")
+    if len(ids) > eng.max_seq:
+        raise ValueError(f"prompt ({len(ids)}) exceeds max_seq {eng.max_seq}")
+    n = len(ids) - 1
+    chunk = max(1, min(SCORE_CHUNK_BYTES // (2 * eng.cfg.head_rows), eng.max_prefill_rows))
+    parts = []
+    eng.seq_len[slot] = 0
+    for c0 in range(0, len(ids), eng.max_prefill_rows):  # the prefill, in chunks the engine's scratch holds
+        c = min(eng.max_prefill_rows, len(ids) - c0)
+        h = eng.forward(eng.embed(torch.tensor(ids[c0:c0 + c], dtype=torch.int64)), [slot] * c,
+                        list(range(c0, c0 + c)))
+        eng.seq_len[slot] = c0 + c
+        for r0 in range(0, min(c, n - c0), chunk):
+            k = min(chunk, min(c, n - c0) - r0)
+            logits = sampler.logits(h, list(range(r0, r0 + k)))
+            lp = sampler.logprobs(logits, ids[c0 + r0 + 1:c0 + r0 + k + 1], top)
+            parts.append([t.cpu() for t in lp])
+            del logits
+    return LP.Logprobs(*(torch.cat([p[i] for p in parts]) for i in range(5)))
+
+
 __all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "SamplingDecodeGraph", "EagerSamplingDecode",
-           "device_params"]
+           "device_params", "score_prompt", "SCORE_CHUNK_BYTES"]

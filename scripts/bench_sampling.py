@@ -16,8 +16,15 @@
    reads (2 x 2 x V per row) and the GB/s they make; and the TPOT of a 7B-shaped ``SamplingDecodeGraph``
    with penalties (temperature 0.7, top-p 0.9, rho 1.1, beta 0.2) against the same graph without.
 
+4. ``--logprobs`` (results: profiles/logprobs.md) instead: ``lsa_logprobs`` alone at 1 and 512 rows
+   of V = 32000 for ``n_top`` 0 and 20 (random targets) next to ``lsa_sample`` (top-p 0.9) on the
+   same logits, back to back and 50 launches in one graph; and the TPOT of a 7B-shaped
+   ``SamplingDecodeGraph`` (temperature 0.7, top-p 0.9) with ``logprobs=5`` against the same graph
+   without, in alternating windows of one process.
+
     python scripts/bench_sampling.py [--layers 32] [--skip-kernel] [--skip-tpot] [--json-out FILE]
     python scripts/bench_sampling.py --penalties [--layers 32] [--json-out FILE]
+    python scripts/bench_sampling.py --logprobs [--layers 32] [--json-out FILE]
 """
 import argparse
 import json
@@ -29,6 +36,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llm_sharding_amd.config import LlamaConfig  # noqa: E402
+from llm_sharding_amd.ops import logprobs as LP  # noqa: E402
 from llm_sharding_amd.ops import penalties as P  # noqa: E402
 from llm_sharding_amd.ops import sampling as S  # noqa: E402
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, StageEngine  # noqa: E402
@@ -215,6 +223,69 @@ def bench_tpot_penalties(layers: int, rows: int, rounds: int = 5, steps: int = 2
             "penalties_spread_ms": round(max(times["penalties"]) - min(times["penalties"]), 4)}
 
 
+def bench_logprobs(rows: int, n_top: int, V: int = 32000, iters: int = 200) -> dict:
+    g = torch.Generator(device=DEV).manual_seed(rows + V)
+    lg = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
+    nt = torch.full((rows,), n_top, dtype=torch.int32, device=DEV)
+    tg = torch.randint(0, V, (rows,), generator=torch.Generator().manual_seed(3)).to(torch.int32).to(DEV)
+    out = LP.alloc_outputs(rows, DEV)
+
+    def run():
+        LP.logprobs(lg, V, rows, nt, tg, out)
+
+    for _ in range(10):
+        run()
+    torch.cuda.synchronize()
+    us = 1e3 * statistics.median(_events(run, iters) for _ in range(5))
+    gus = 1e3 * _graph_events(run, 50)
+    return {"kernel": "lsa_logprobs", "rows": rows, "V": V, "n_top": n_top, "us": round(us, 2),
+            "graphed_us": round(gus, 2), "pass_MB": round(rows * V * 2 / 1e6, 2)}
+
+
+def bench_tpot_logprobs(layers: int, rows: int, n_top: int = 5, rounds: int = 5, steps: int = 20) -> dict:
+    cfg = LlamaConfig(num_hidden_layers=layers, vocab_size=32000, max_position_embeddings=512, name=f"7B-{layers}L")
+    eng = StageEngine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                      max_slots=rows, max_seq=128, max_prefill_rows=max(rows, 128))
+    graphs = {"sampling": SamplingDecodeGraph(eng, rows, "full"),
+              "logprobs": SamplingDecodeGraph(eng, rows, "full", logprobs=True)}
+    for r in range(rows):
+        graphs["sampling"].set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r))
+        graphs["logprobs"].set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r, logprobs=n_top))
+    for g in graphs.values():
+        g.capture()
+    tok0 = torch.randint(3, cfg.vocab_size, (rows,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(DEV)
+    times = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            g.set_positions()
+            g.tokens.copy_(tok0)
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            times[name].append(_events(g.replay, steps))
+    ts, tl = statistics.median(times["sampling"]), statistics.median(times["logprobs"])
+    del graphs, eng
+    torch.cuda.empty_cache()
+    return {"layers": layers, "rows": rows, "n_top": n_top, "sampling_ms": round(ts, 4), "logprobs_ms": round(tl, 4),
+            "delta_ms": round(tl - ts, 4), "delta_pct": round(100 * (tl - ts) / ts, 2),
+            "sampling_spread_ms": round(max(times["sampling"]) - min(times["sampling"]), 4),
+            "logprobs_spread_ms": round(max(times["logprobs"]) - min(times["logprobs"]), 4)}
+
+
+def main_logprobs(a) -> dict:
+    out = {"kernel": [], "tpot": []}
+    for rows in (1, 512):
+        for r in (bench_logprobs(rows, 0), bench_logprobs(rows, 20), bench_kernel(rows, 32000, "top_p", graphed=True)):
+            out["kernel"].append(r)
+            print(json.dumps(r), flush=True)
+    if not a.skip_tpot:
+        for rows in (1, 512):
+            r = bench_tpot_logprobs(a.layers, rows)
+            out["tpot"].append(r)
+            print(json.dumps(r), flush=True)
+    return out
+
+
 def main_penalties(a) -> dict:
     out = {"kernel": [], "tpot": []}
     for rows in (1, 512):
@@ -235,18 +306,20 @@ def main():
     ap.add_argument("--skip-tpot", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--penalties", action="store_true", help="measure lsa_penalize and the penalised step instead")
+    ap.add_argument("--logprobs", action="store_true", help="measure lsa_logprobs and the step with logprobs=5 instead")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sampling.py measures on the GPU: none found")
-    out = main_penalties(a) if a.penalties else {"kernel": [], "tpot": []}
-    for V in (() if a.skip_kernel or a.penalties else (32000, 128256)):
+    special = a.penalties or a.logprobs
+    out = main_penalties(a) if a.penalties else (main_logprobs(a) if a.logprobs else {"kernel": [], "tpot": []})
+    for V in (() if a.skip_kernel or special else (32000, 128256)):
         for rows in (1, 128, 512):
             for mode in ("temperature", "top_k", "top_p"):
                 r = bench_kernel(rows, V, mode)
                 out["kernel"].append(r)
                 print(json.dumps(r), flush=True)
-    if not a.skip_tpot and not a.penalties:
+    if not a.skip_tpot and not special:
         for rows in (1, 512):
             r = bench_tpot(a.layers, rows)
             out["tpot"].append(r)

@@ -22,9 +22,11 @@ finished request to stdout and, if ``reply_to`` is given, pushes ``{"request_id"
 "shutdown"}`` drains the queue and stops every rank. Optional ``temperature``, ``top_k``,
 ``top_p`` and ``seed`` keys of a request sample on the device instead of greedy decode (one
 pipeline stage only), and ``repetition_penalty``, ``presence_penalty`` and ``frequency_penalty``
-keys penalise repeated tokens on the device (also at temperature 0; one stage only);
-``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty`` do
-the same for the synthetic load test (request i seeded with ``--seed`` + i).
+keys penalise repeated tokens on the device (also at temperature 0; one stage only); a
+``logprobs`` key (0..20) adds a ``"logprobs"`` dict to the reply: per-token ``token_logprobs``,
+``ranks`` and that many ``top_logprobs`` alternatives (one stage only);
+``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty
+--logprobs`` do the same for the synthetic load test (request i seeded with ``--seed`` + i).
 """
 import argparse
 import json
@@ -69,6 +71,8 @@ def main():
                                                                           "(1: off; one stage only)")
     ap.add_argument("--presence-penalty", type=float, default=0.0)
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N",
+                    help="load test: collect per-token log-probabilities and N (0..20) alternatives (one stage only)")
     a = ap.parse_args()
     if a.random:
         a.model = a.random
@@ -124,10 +128,11 @@ def main():
         for i in range(a.requests):
             ids = torch.randint(3, cfg.vocab_size, (a.prompt_len,), generator=g).tolist()
             pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
-            if a.temperature > 0 or pen != (1.0, 0.0, 0.0):
+            if a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None:
                 from llm_sharding_amd.runtime.sampling import SamplingParams
                 srv.submit(ids, rc.max_new_tokens, eos_ids=(),
-                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i, *pen))
+                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i, *pen,
+                                                   logprobs=a.logprobs))
             else:
                 srv.submit(ids, rc.max_new_tokens, eos_ids=())
         t0 = time.perf_counter()
