@@ -20,7 +20,13 @@ class Replies:
     """on_token callback: prints each finished request and pushes ``{"request_id",
     "output_ids", "text", "ttft_ms", "tpot_ms"}`` to its ``reply_to`` address - plus a
     ``"logprobs"`` dict (``token_logprobs``, ``ranks`` and, with ``logprobs >= 1``, ``top_logprobs``:
-    per token a list of ``[id, logprob]`` pairs) for a request that asked for them."""
+    per token a list of ``[id, logprob]`` pairs) for a request that asked for them. The children of
+    a request with ``n > 1`` are answered together, when the last one is done: the reply is child
+    0's, plus a ``"choices"`` list with one such dict (and its ``"index"``) per child, in seed order.
+    If some children will never finish (:meth:`error` with their ``request_id``), the finished ones
+    are still sent, as soon as every child is finished or failed: the reply is then the first
+    finished child's and ``"choices"`` holds the finished children only, each with the ``"index"``
+    of its seed."""
 
     def __init__(self, tokenizer=None, verbose: bool = True, on_done: Optional[Callable] = None):
         self.tok = tokenizer
@@ -30,6 +36,25 @@ class Replies:
         # __call__ runs on the serve thread, error() on the listener thread: one lock guards the
         # socket table and the sends (one PushSocket per reply_to, never two racing creations)
         self._lock = threading.Lock()
+        self._groups: dict = {}  # n > 1: groups with a finished child, waiting for their siblings
+
+    def _group_done(self, g: dict, reply: Optional[dict], reply_to: str) -> Optional[dict]:
+        """One more child of ``g`` finished (``reply``) or failed (None): the group's reply once
+        every child is accounted for and at least one finished, else None."""
+        with self._lock:
+            if reply is not None:
+                g.setdefault("replies", []).append(reply)
+                self._groups[id(g)] = (g, reply_to)
+            else:
+                g["failed"] = g.get("failed", 0) + 1
+            got = g.get("replies", [])
+            if not got or len(got) + g.get("failed", 0) < g["n"]:
+                return None
+            self._groups.pop(id(g), None)
+        rids = g.get("rids", [])
+        choices = sorted(got, key=lambda c: c["request_id"])  # seed order
+        return dict(choices[0], choices=[dict(c, index=rids.index(c["request_id"]) if c["request_id"] in rids else i)
+                                         for i, c in enumerate(choices)])
 
     def _send(self, reply_to: str, payload: bytes) -> None:
         with self._lock:
@@ -54,6 +79,11 @@ class Replies:
                 reply["logprobs"] = {"token_logprobs": list(r.token_logprobs), "ranks": list(r.ranks)}
                 if r.top_logprobs is not None:
                     reply["logprobs"]["top_logprobs"] = [[[int(i), float(v)] for i, v in t] for t in r.top_logprobs]
+            g = getattr(r, "group", None)
+            if g is not None and g.get("n", 1) > 1:  # a child of n samples: one reply, when the last is done
+                reply = self._group_done(g, reply, r.reply_to)
+                if reply is None:
+                    return
             self._send(r.reply_to, protocol.encode(reply))
 
     def error(self, reply_to: Optional[str], reason: str, request_id=None) -> None:
@@ -65,6 +95,12 @@ class Replies:
         try:
             self._send(reply_to, protocol.encode({"request_id": request_id, "error": reason,
                                                   "output_ids": [], "text": ""}))
+            with self._lock:  # a child of n samples: its finished siblings must not wait for it for ever
+                hit = [(g, to) for g, to in self._groups.values() if request_id in g.get("rids", ())]
+            for g, to in hit:
+                reply = self._group_done(g, None, to)
+                if reply is not None:
+                    self._send(to, protocol.encode(reply))
         except OSError as e:
             print(f"[WARNING] error reply to {reply_to} failed: {e}", flush=True)
 
@@ -86,8 +122,12 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     when none is given; optional ``repetition_penalty``, ``presence_penalty``,
     ``frequency_penalty``: penalties on repeated tokens, with or without a temperature; optional
     ``logprobs`` (0..20): per-token log-probabilities, ranks and that many alternatives in the
-    reply). Returns the number of requests queued."""
+    reply; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
+    optional ``n > 1``: that many samples of each prompt sharing one prefill, answered with a
+    ``"choices"`` list - needs a server with ``prefix_slots``). Returns the number of requests
+    queued."""
     n_new = int(msg.get("max_new_tokens") or default_new)
+    samples = int(msg.get("n") or 1)
     rows = msg.get("input_ids")
     if rows is None:
         if tokenizer is None:
@@ -102,6 +142,11 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
             # optional temperature / top_k / top_p / seed / *_penalty / logprobs keys; absent: greedy (the plain call)
             sp = SamplingParams.from_dict(msg)
             kw = {} if sp is None else {"sampling": sp}
+            if samples != 1:
+                n += len(srv.submit_n(ids, samples, n_new, on_token=replies, reply_to=msg.get("reply_to"), **kw))
+                continue
+            if msg.get("cache_prefix") is not None:
+                kw["cache_prefix"] = int(msg["cache_prefix"])
             srv.submit(ids, n_new, on_token=replies, reply_to=msg.get("reply_to"), **kw)
             n += 1
         except ValueError as e:

@@ -23,6 +23,17 @@ A slot whose request finished is re-armed (device position reset) with the next 
 its micro-batch; a free slot still rides along in graph replays (its outputs are ignored),
 which keeps the graph static.
 
+Prefix pool (``prefix_slots=P``): the engine gets ``B * M + P`` KV slots; slots ``>= B * M`` are
+never decoded and belong to no micro-batch or graph. A request that declares ``cache_prefix=L``
+has ``input_ids[:L]`` prefilled into a pool slot (ordinary ``PREFILL`` items ``(pool_slot, p0, n,
+0)`` in its own micro-batch's commands), and every admitted request forks the longest pooled match
+of its prompt into its slot with ``FORK`` - items ``(src, dst, len, 0)``, executed by every rank on
+its own layers (:func:`..ops.kvcache.fork_jobs`), nothing returned - and prefills only the rest.
+:meth:`submit_n` queues ``n`` samples of one prompt behind one prefill the same way. Rank 0 keeps
+the registry (tokens, ready flag, pin count, LRU stamp per pool slot); with ``streams > 1`` a fork
+waits on the event of the command that finished filling its entry, and the refill of an evicted
+entry on the events of the forks that read it.
+
 Live re-sharding (the reference's hot re-configuration, ``/root/reference/utils/node_worker.py
 :445-474``, on the deployed pipeline): :meth:`request_replan` (rank 0; the master's ``replan``
 command arrives through the ingress) stops admitting requests, lets every request in flight
@@ -47,8 +58,16 @@ from ..runtime.sampling import SamplingParams
 from ..utils import tracing
 from .pipeline import DistP2P, _percentile
 
-CMD_DECODE, CMD_PREFILL, CMD_STOP, CMD_REPLAN = 1, 2, 3, 4
+CMD_DECODE, CMD_PREFILL, CMD_STOP, CMD_REPLAN, CMD_FORK = 1, 2, 3, 4, 5
 WAITING, PREFILLING, DECODING, DONE = "waiting", "prefilling", "decoding", "done"
+FORKING = "forking"  # admitted, waiting to fork its prefix from a pool entry
+
+# Default of ``prefix_min_match``: the shortest undeclared match worth a fork. Measured on an MI355X
+# (profiles/kv_fork.md part b, scripts/bench_prefix.py breakeven; Llama-2-7B): fork(j) + a suffix
+# prefill against a whole prefill of j + suffix tokens, suffixes 32, 31 and 1. j = 1 loses 0.03 -
+# 0.04 ms at two of the three suffixes (the fork costs 0.06 ms and a prefill command's time is a step
+# function of its rows); j = 8 is the smallest measured j that wins at all three (by 0.09 - 0.46 ms).
+PREFIX_MIN_MATCH = 8
 
 
 @dataclass
@@ -71,6 +90,10 @@ class Request:
     t_submit: float = 0.0
     t_first: float = 0.0
     t_done: float = 0.0
+    cache_prefix: Optional[int] = None  # declared: input_ids[:cache_prefix] is worth keeping in the pool
+    group: Optional[dict] = None  # submit_n: the state its children share
+    entry: Optional["_PoolEntry"] = None  # FORKING: the pool entry it forks from ...
+    fork_len: int = 0  # ... and how many tokens
 
     @property
     def ttft_ms(self) -> float:
@@ -82,9 +105,26 @@ class Request:
         return (self.t_done - self.t_first) * 1e3 / (n - 1) if n > 1 else 0.0
 
 
+@dataclass(eq=False)
+class _PoolEntry:
+    """One slot of the prefix pool (rank 0's registry)."""
+    slot: int
+    tokens: List[int]
+    filler: Optional[Request] = None  # the request whose micro-batch carries the fill
+    filled: int = 0  # tokens of the fill issued so far
+    ready: bool = False  # the whole fill is issued: later commands may fork from it
+    pins: int = 0  # admitted requests (and unadmitted submit_n children) that have yet to fork from it
+    stamp: int = 0  # least recently used = smallest
+    fill_event: object = None  # streams > 1: recorded behind the last fill command
+
+    @property
+    def length(self) -> int:
+        return len(self.tokens)
+
+
 class _Header:
     """int32 command header: [cmd, mb, n_items, n_resets, items (slot, p0, n, emit)..., resets...];
-    REPLAN: [cmd, 0, world + 1, 0, stage boundaries...]."""
+    FORK: items are (src, dst, len, 0); REPLAN: [cmd, 0, world + 1, 0, stage boundaries...]."""
 
     def __init__(self, batch: int, world: int = 1):
         self.size = 4 + max(4 * batch + batch, world + 1)
@@ -118,8 +158,22 @@ class PipelineServer:
     def __init__(self, cfg, source, rank: int = 0, world: int = 1, start: int = 0, end: Optional[int] = None,
                  device="cpu", batch: int = 8, microbatches: int = 1, max_seq: int = 2048,
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
-                 ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1):
+                 ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
+                 prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH):
         self.cfg, self.rank, self.world = cfg, rank, world
+        # prefix pool: engine slots >= B * M, never decoded, in no micro-batch and no graph
+        self.P = int(prefix_slots)
+        if self.P < 0 or int(prefix_min_match) < 1:
+            raise ValueError("prefix_slots must be >= 0 and prefix_min_match >= 1")
+        if self.P > 0 and not causal:
+            raise ValueError("prefix caching needs causal attention: under the unmasked prefill a prefix's K/V "
+                             "depend on the tokens after it")
+        self.prefix_min_match = int(prefix_min_match)
+        self.pool: List[Optional[_PoolEntry]] = [None] * self.P
+        self._pool_reads: List[list] = [[] for _ in range(self.P)]  # fork events that outlive an evicted entry
+        self._stamp = 0
+        self.prefix_stats = {"prefix_hits": 0, "prefix_tokens_forked": 0, "prefix_fills": 0, "prefix_evictions": 0,
+                             "prefix_bypass": 0}
         end = cfg.num_hidden_layers if end is None else end
         self.first, self.last = rank == 0, rank == world - 1
         self.B, self.M = batch, microbatches
@@ -174,7 +228,7 @@ class PipelineServer:
     # ------------------------------------------------------------------ engine (re)build
     def _build_engine(self, start: int, end: int) -> StageEngine:
         return StageEngine(self.cfg, start, end, self.device, self.dtype, has_embed=self.first, has_head=self.last,
-                           source=self.source, max_slots=self.B * self.M, max_seq=self.max_seq,
+                           source=self.source, max_slots=self.B * self.M + self.P, max_seq=self.max_seq,
                            max_prefill_rows=max(self.budget, self.B), causal=self.causal)
 
     def _build_graphs(self) -> None:
@@ -320,6 +374,9 @@ class PipelineServer:
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
+        # the pool's K/V went with the engine: same prefix_slots, empty registry
+        self.pool = [None] * self.P
+        self._pool_reads = [[] for _ in range(self.P)]
         self.cur_tok.clear()
         self.pending_resets = [[] for _ in range(self.M)]
         self.replans += 1
@@ -365,7 +422,7 @@ class PipelineServer:
 
     def _set_pos(self, slot: int, p: int) -> None:
         self.eng.seq_len[slot] = p
-        if self.graph_mode:
+        if self.graph_mode and slot < self.B * self.M:  # a pool slot has no device position
             mb, i = divmod(slot, self.B)
             self.graphs[mb].pos[i] = p
 
@@ -412,7 +469,7 @@ class PipelineServer:
     # ------------------------------------------------------------------ command execution (every rank)
     def _exec(self, cmd, mb, items, resets, ids=None):
         """Run one command on this stage. Returns the last stage's token ids (world == 1)."""
-        name = {CMD_PREFILL: "prefill", CMD_DECODE: "decode"}.get(cmd, "cmd")
+        name = {CMD_PREFILL: "prefill", CMD_DECODE: "decode", CMD_FORK: "fork"}.get(cmd, "cmd")
         with self.tl.span(name, mb=mb, items=len(items)), self._mb_ctx(mb):
             return self._exec_body(cmd, mb, items, resets, ids)
 
@@ -420,6 +477,16 @@ class PipelineServer:
         eng, H = self.eng, self.cfg.hidden_size
         for s in resets:
             self._set_pos(s, 0)
+        if cmd == CMD_FORK:  # items (src, dst, len, 0) on this stage's layers; nothing returns
+            from ..ops.kvcache import MAX_FANOUT, fork_jobs
+            by_src: Dict[tuple, list] = {}
+            for (src, dst, n, _) in items:
+                by_src.setdefault((src, n), []).append(dst)
+            fork_jobs(eng, [(src, n, d[i:i + MAX_FANOUT]) for (src, n), d in by_src.items()
+                            for i in range(0, len(d), MAX_FANOUT)])
+            for (_, dst, n, _) in items:
+                self._set_pos(dst, n)
+            return None
         if cmd == CMD_PREFILL:
             slot, pos, emit_rows = [], [], []
             for (s, p0, n, emit) in items:
@@ -505,8 +572,12 @@ class PipelineServer:
 
     # ------------------------------------------------------------------ rank 0: requests
     def submit(self, input_ids, max_new_tokens: int = 64, eos_ids=None, on_token=None,
-               reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> int:
-        """Queue a request (thread-safe). ``input_ids``: list of token ids. ``sampling``:
+               reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None, *,
+               cache_prefix: Optional[int] = None, _group: Optional[dict] = None) -> int:
+        """Queue a request (thread-safe). ``input_ids``: list of token ids. ``cache_prefix=L``
+        (a server with ``prefix_slots``): ``input_ids[:L]`` is worth keeping - it is prefilled into
+        a pool slot once and forked from there by this and later requests (``L`` is clamped to
+        ``len - 1``: the last prompt token is always computed). ``sampling``:
         temperature / top-k / top-p / seed, repetition / presence / frequency penalties and
         ``logprobs`` of the request (None, or temperature 0 with every penalty off and no logprobs:
         greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
@@ -529,10 +600,34 @@ class PipelineServer:
             rid = self._next_id
             self._next_id += 1
         eos = tuple(self.cfg.eos_ids if eos_ids is None else eos_ids)
+        if cache_prefix is not None:
+            cache_prefix = max(0, min(int(cache_prefix), len(ids) - 1))
         r = Request(rid, ids, int(max_new_tokens), eos, on_token=on_token, reply_to=reply_to, sampling=sampling,
-                    t_submit=time.perf_counter())
+                    t_submit=time.perf_counter(), cache_prefix=cache_prefix, group=_group)
         self.incoming.put(r)
         return rid
+
+    def submit_n(self, input_ids, n: int, max_new_tokens: int = 64, eos_ids=None, on_token=None,
+                 reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> List[int]:
+        """Queue ``n`` samples of one prompt that share one prefill (thread-safe): ``input_ids[:-1]``
+        becomes a pool entry, pinned until the last child has forked from it, and child ``i`` is an
+        ordinary request with ``seed + i`` (``seed=None``: one drawn seed plus ``i``) and
+        ``cache_prefix = len - 1``. Children admitted in the same scheduling round share one
+        fan-out fork. Returns the children's request ids, in seed order."""
+        import dataclasses
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"submit_n: n must be >= 1, got {n}")
+        if self.P < 1:
+            raise ValueError("submit_n needs a prefix pool: build the server with prefix_slots >= 1")
+        ids = [int(x) for x in input_ids]
+        rids: List[int] = []
+        group = {"n": n, "left": n, "entry": None, "rids": rids}
+        for i in range(n):
+            sp = None if sampling is None else dataclasses.replace(sampling, seed=(sampling.seed + i) % (1 << 64))
+            rids.append(self.submit(ids, max_new_tokens, eos_ids, on_token, reply_to, sp,
+                                    cache_prefix=len(ids) - 1, _group=group))
+        return rids
 
     def unfinished(self) -> List[Request]:
         """Rank 0, after :meth:`serve` has returned: every request that will never finish here
@@ -552,6 +647,104 @@ class PipelineServer:
 
     def _free_slots(self, mb: int) -> list:
         return [s for s in self._slots(mb) if s not in self.by_slot]
+
+    # ------------------------------------------------------------------ rank 0: prefix pool
+    @staticmethod
+    def _common(a: list, b: list, cap: int) -> int:
+        """Length of the common token prefix of ``a`` and ``b``, at most ``cap``."""
+        n, i = min(len(a), len(b), cap), 0
+        while i < n and a[i] == b[i]:
+            i += 1
+        return i
+
+    def _pool_take(self, tokens: list, filler: Request) -> Optional[_PoolEntry]:
+        """A pool slot for a new entry: a free one, else the least recently used unpinned one
+        (evicted). None when every slot is pinned."""
+        i = next((i for i, e in enumerate(self.pool) if e is None), None)
+        if i is None:
+            cand = [e for e in self.pool if e.pins == 0 and e.ready]
+            if not cand:
+                return None
+            i = min(cand, key=lambda e: e.stamp).slot - self.B * self.M
+            self.prefix_stats["prefix_evictions"] += 1
+        e = self.pool[i] = _PoolEntry(self.B * self.M + i, list(tokens), filler=filler)
+        self.prefix_stats["prefix_fills"] += 1
+        return e
+
+    def _attach(self, r: Request) -> None:
+        """Admission of ``r``: choose the pool entry it forks from (a ready one, one that is being
+        filled with its declared prefix, or a new one whose fill rides with ``r``'s micro-batch)
+        and pin it; without one ``r`` stays an ordinary request."""
+        ids, cap, g = r.input_ids, len(r.input_ids) - 1, r.group
+        if g is not None:
+            g["left"] -= 1  # children still to be admitted
+        e, j, pinned = None, 0, False
+        if g is not None and g["entry"] is not None and not any(c is g["entry"] for c in self.pool):
+            g["entry"] = None  # a re-plan dropped the registry: the siblings' entry and its K/V are gone
+        if g is not None and g["entry"] is not None:  # a sibling chose the entry and pinned it for r
+            e, pinned = g["entry"], True
+            j = self._common(e.tokens, ids, cap)
+        else:
+            L = r.cache_prefix or 0
+            for c in self.pool:  # the longest match; a declared prefix may also wait for its fill
+                if c is None:
+                    continue
+                cj = self._common(c.tokens, ids, cap)
+                if cj > j and (cj >= L if L and not c.ready else c.ready):
+                    e, j = c, cj
+            if L and j < L:  # no entry covers the declared prefix: insert it
+                e = self._pool_take(ids[:L], r)
+                j = L
+                if e is None:
+                    self.prefix_stats["prefix_bypass"] += 1
+                    e, j = None, 0
+                    for c in self.pool:
+                        cj = self._common(c.tokens, ids, cap) if c is not None and c.ready else 0
+                        if cj > j:
+                            e, j = c, cj
+            if e is not None and not (L and j >= L) and j < self.prefix_min_match:
+                e = None
+        if e is None:
+            return
+        if not pinned:
+            e.pins += 1
+        if g is not None and g["entry"] is None:
+            g["entry"] = e
+            e.pins += g["left"]
+        self._stamp += 1
+        e.stamp = self._stamp
+        if e.filler is not r:
+            self.prefix_stats["prefix_hits"] += 1
+            self.prefix_stats["prefix_tokens_forked"] += j
+        r.entry, r.fork_len, r.state = e, j, FORKING
+
+    def _issue_forks(self, mb: int) -> None:
+        """Fork the prefix of every request of ``mb`` whose entry is ready: one ``CMD_FORK`` (items
+        that share a source become one fan-out job), which returns nothing; the requests then
+        prefill from their fork length."""
+        rs = [r for r in (self.by_slot.get(s) for s in self._slots(mb))
+              if r is not None and r.state == FORKING and r.entry.ready]
+        if not rs:
+            return
+        items = [(r.entry.slot, r.slot, r.fork_len, 0) for r in rs]
+        self._bcast_header(self.hdr.pack(CMD_FORK, mb, items, []))
+        entries = list({id(r.entry): r.entry for r in rs}.values())
+        if self.S > 1:  # the fill ran on its own micro-batch's stream
+            with self._mb_ctx(mb):
+                for e in entries:
+                    if e.fill_event is not None:
+                        torch.cuda.current_stream(self.device).wait_event(e.fill_event)
+        self._exec(CMD_FORK, mb, items, [])
+        if self.S > 1:  # a refill of an evicted entry waits for the forks that read its slot
+            with self._mb_ctx(mb):
+                ev = torch.cuda.Event()
+                ev.record()
+            for e in entries:
+                i = e.slot - self.B * self.M
+                self._pool_reads[i] = [x for x in self._pool_reads[i] if not x.query()] + [ev]
+        for r in rs:
+            r.entry.pins -= 1
+            r.entry, r.prefilled, r.state = None, r.fork_len, PREFILLING
 
     def _emit(self, r: Request, tok: int, now: float) -> None:
         if not r.output_ids:
@@ -644,9 +837,35 @@ class PipelineServer:
             self.by_slot[s] = r
             if s in resets:
                 resets.remove(s)
+            if self.P:
+                self._attach(r)
+        fills = []
+        if self.P:
+            self._issue_forks(mb)
+            # requests of mb whose pool entry is still to be filled: the fill rides with mb's prefills
+            fills = [r.entry for r in (self.by_slot.get(s) for s in self._slots(mb))
+                     if r is not None and r.state == FORKING and r.entry.filler is r and not r.entry.ready]
         pre = [self.by_slot[s] for s in self._slots(mb) if s in self.by_slot and self.by_slot[s].state == PREFILLING]
-        if pre:
+        if pre or fills:
             items, ids, info, budget = [], [], [], self.budget
+            filled = []
+            for e in fills:  # ordinary prefill items (pool_slot, p0, n, 0), chunked by the budget
+                if budget <= 0:
+                    break
+                n = min(e.length - e.filled, budget)
+                if e.filled == 0 and self.S > 1:  # the forks that still read the evicted entry's slot
+                    i = e.slot - self.B * self.M
+                    with self._mb_ctx(mb):
+                        for ev in self._pool_reads[i]:
+                            torch.cuda.current_stream(self.device).wait_event(ev)
+                    self._pool_reads[i] = []
+                items.append((e.slot, e.filled, n, 0))
+                ids += e.tokens[e.filled:e.filled + n]
+                info.append(None)
+                e.filled += n
+                budget -= n
+                if e.filled == e.length:
+                    filled.append(e)
             for r in pre:
                 if budget <= 0:
                     break
@@ -658,6 +877,12 @@ class PipelineServer:
                 r.prefilled += n
                 budget -= n
             self._issue(CMD_PREFILL, mb, items, resets, ids, info)
+            for e in filled:  # every command issued from here on is ordered behind the whole fill
+                e.ready, e.filler = True, None
+                if self.S > 1:
+                    with self._mb_ctx(mb):
+                        e.fill_event = torch.cuda.Event()
+                        e.fill_event.record()
             return True
         dec = [self.by_slot[s] for s in self._slots(mb) if s in self.by_slot and self.by_slot[s].state == DECODING]
         if dec:
@@ -767,6 +992,9 @@ class PipelineServer:
             "ttft_ms_p50": _percentile([r.ttft_ms for r in done], 0.5),
             "tpot_ms_p50": _percentile([r.tpot_ms for r in done if len(r.output_ids) > 1], 0.5),
             "tpot_ms_p90": _percentile([r.tpot_ms for r in done if len(r.output_ids) > 1], 0.9),
+            # prefix pool: requests that forked K/V computed for another request and the prefill tokens
+            # that saved them, pool entries filled / evicted, declared prefixes that found every slot pinned
+            **self.prefix_stats,
         }
 
 

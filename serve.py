@@ -27,6 +27,11 @@ keys penalise repeated tokens on the device (also at temperature 0; one stage on
 ``ranks`` and that many ``top_logprobs`` alternatives (one stage only);
 ``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty
 --logprobs`` do the same for the synthetic load test (request i seeded with ``--seed`` + i).
+``--prefix-slots P`` adds a pool of P KV slots for shared prompt prefixes: a request's
+``cache_prefix`` key declares its leading tokens worth keeping, every request forks the longest
+pooled match instead of prefilling it, and an ``n`` key asks for that many samples of one prompt
+behind one prefill (the reply then carries a ``"choices"`` list). ``--shared-prefix-len L`` gives
+the load test's requests the same first L tokens, declared; ``--n N`` makes each of them N samples.
 """
 import argparse
 import json
@@ -73,6 +78,11 @@ def main():
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
     ap.add_argument("--logprobs", type=int, default=None, metavar="N",
                     help="load test: collect per-token log-probabilities and N (0..20) alternatives (one stage only)")
+    ap.add_argument("--prefix-slots", type=int, default=0, metavar="P",
+                    help="KV slots of the prefix pool (0: no prefix caching, no parallel samples)")
+    ap.add_argument("--shared-prefix-len", type=int, default=0, metavar="L",
+                    help="load test: every request starts with the same L tokens and declares them")
+    ap.add_argument("--n", type=int, default=1, metavar="N", help="load test: N samples per prompt (submit_n)")
     a = ap.parse_args()
     if a.random:
         a.model = a.random
@@ -108,39 +118,46 @@ def main():
         for _ in range(8):  # the KV budget moves layer boundaries: iterate to a fixed point
             rc.batch = min(kv_slots_for_memory(cfg, s.n_layers, rc.max_seq, mem, s.weight_bytes, reserve_bytes=reserve,
                                                microbatches=M) for s in plan.stages)
-            nxt = plan_stages(cfg, world, kv_tokens=rc.max_seq * rc.batch * M)
+            rc.batch = max(1, (rc.batch * M - a.prefix_slots) // M)  # the pool's slots come out of the same HBM
+            nxt = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots))
             if nxt.ranges() == plan.ranges():
                 break
             plan = nxt
         log.info(f"KV cache sized from {mem / 1e9:.0f} GB HBM: {rc.batch} slots x {M} micro-batches")
-    plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * rc.batch * M)
+    plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots))
     st = plan.stages[rank]
     if rank == 0:
         log.info(f"{cfg.name}: {world} stage(s) {plan.ranges()}, {M} x {rc.batch} slots")
     srv = PipelineServer(cfg, source, rank, world, st.start, st.end, dev, batch=rc.batch, microbatches=M,
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
-                         streams=rc.streams)
+                         streams=rc.streams, prefix_slots=a.prefix_slots)
     if rank != 0:
         srv.serve()
     elif a.requests:
         g = torch.Generator().manual_seed(rc.seed + 1)
+        shared = torch.randint(3, cfg.vocab_size, (min(a.shared_prefix_len, a.prompt_len),), generator=g).tolist()
         for i in range(a.requests):
-            ids = torch.randint(3, cfg.vocab_size, (a.prompt_len,), generator=g).tolist()
+            ids = shared + torch.randint(3, cfg.vocab_size, (a.prompt_len - len(shared),), generator=g).tolist()
             pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
+            kw = {}
             if a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None:
                 from llm_sharding_amd.runtime.sampling import SamplingParams
-                srv.submit(ids, rc.max_new_tokens, eos_ids=(),
-                           sampling=SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i, *pen,
-                                                   logprobs=a.logprobs))
+                kw["sampling"] = SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i * a.n, *pen,
+                                                logprobs=a.logprobs)
+            if a.n > 1:
+                srv.submit_n(ids, a.n, rc.max_new_tokens, eos_ids=(), **kw)
+            elif shared and a.prefix_slots:
+                srv.submit(ids, rc.max_new_tokens, eos_ids=(), cache_prefix=len(shared), **kw)
             else:
-                srv.submit(ids, rc.max_new_tokens, eos_ids=())
+                srv.submit(ids, rc.max_new_tokens, eos_ids=(), **kw)
         t0 = time.perf_counter()
         srv.t_start = t0
         srv.serve(stop_when_idle=True)
         s = srv.stats()
         s.update({"metric": "serving_output_tokens_per_sec", "n_gpus": world, "model": cfg.name,
-                  "requests": a.requests, "prompt_len": a.prompt_len, "max_new_tokens": rc.max_new_tokens,
+                  "requests": a.requests * a.n, "prompt_len": a.prompt_len, "max_new_tokens": rc.max_new_tokens,
+                  "prefix_slots": a.prefix_slots, "shared_prefix_len": len(shared), "n": a.n,
                   "slots": rc.batch * M, "microbatches": M})
         print(json.dumps(s), flush=True)
     else:
