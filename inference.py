@@ -10,6 +10,9 @@ or without a temperature (temperature 0: the arg-max of the penalised logits).
 ``--logprobs N`` (0..20) prints each generated token's log-probability, rank and N most likely
 alternatives (of the penalised logits at temperature 1, before top-k / top-p); ``--score`` prints the
 prompt's own per-token log-probabilities, mean NLL and perplexity instead of generating.
+``--speculative K [--spec-ngram MIN,MAX]`` decodes speculatively: K tokens drafted from the sequence's
+own history (the longest n-gram match of MIN..MAX tokens) are verified in one step of K + 1 rows; the
+output is the plain output, greedy or sampled, in fewer steps when the text repeats itself.
 
     python inference.py --shards DIR [--prompt "..."] [--max-new-tokens 128]
     python inference.py --random llama2-7b --max-new-tokens 64     # random-init weights
@@ -18,6 +21,7 @@ prompt's own per-token log-probabilities, mean NLL and perplexity instead of gen
     python inference.py --random llama2-7b --repetition-penalty 1.2
     python inference.py --shards DIR --logprobs 5
     python inference.py --shards DIR --score --prompt "..."
+    python inference.py --shards DIR --speculative 3 [--temperature 0.7 --top-p 0.9 --seed 1]
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
 (/root/reference/inference.py:16-45: transformers' AutoModelForCausalLM + greedy generate) on the
@@ -60,7 +64,33 @@ def build_parser() -> argparse.ArgumentParser:
                     help="print each generated token's log-probability, rank and N (0..20) alternatives")
     ap.add_argument("--score", action="store_true",
                     help="score the prompt instead of generating: per-token log-probabilities, mean NLL, perplexity")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K",
+                    help="speculative decoding: verify K (1..15) n-gram drafts per step (0: off)")
+    ap.add_argument("--spec-ngram", default="1,3", metavar="MIN,MAX",
+                    help="n-gram lengths (1 <= MIN <= MAX <= 8) of the draft lookup")
     return ap
+
+
+def speculative_from_args(a, sp):
+    """--speculative / --spec-ngram: None without the flag, else (k, (nmin, nmax)); exits on a value
+    out of range or a flag speculation does not combine with."""
+    if a.speculative == 0:
+        return None
+    from llm_sharding_amd.ops.speculative import MAX_K, MAX_NGRAM
+    if not 1 <= a.speculative <= MAX_K:
+        raise SystemExit(f"[ERROR] --speculative K must be in [1, {MAX_K}]")
+    try:
+        nmin, nmax = (int(x) for x in a.spec_ngram.split(","))
+    except ValueError:
+        raise SystemExit("[ERROR] --spec-ngram takes MIN,MAX")
+    if not 1 <= nmin <= nmax <= MAX_NGRAM:
+        raise SystemExit(f"[ERROR] --spec-ngram needs 1 <= MIN <= MAX <= {MAX_NGRAM}")
+    if a.score or a.hf_compare:
+        raise SystemExit("[ERROR] --speculative does not combine with --score or --hf-compare")
+    if sp is not None and (sp.penalized or sp.logprobs is not None):
+        raise SystemExit("[ERROR] --speculative does not combine with the penalty flags or --logprobs "
+                         "(their state is sequential per token)")
+    return a.speculative, (nmin, nmax)
 
 
 def sampling_from_args(a):
@@ -78,6 +108,7 @@ def sampling_from_args(a):
 def main(argv=None):
     a = build_parser().parse_args(argv)
     sp = sampling_from_args(a)
+    spec = speculative_from_args(a, sp)
     if sp is not None and a.hf_compare:
         raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling and penalty flags")
     if a.shards:
@@ -97,6 +128,12 @@ def main(argv=None):
     slot, pos = eng.prefill_rows([0], [ids.numel()])
     h = eng.forward(eng.embed(ids.to(a.device)), slot, pos)
     eng.advance([0], [ids.numel()])
+    if spec is not None:
+        out, dt_s, st = speculative_tokens(eng, h, ids.tolist(), a.max_new_tokens, spec[0], spec[1], sp, cfg.eos_ids)
+        out = report(a, cfg, tok, ids, out, dt_s)
+        print(f"[INFO] speculative k={spec[0]} n-gram {spec[1][0]}..{spec[1][1]}: {st['tokens']} tokens in {st['steps']} "
+              f"steps, {st['tokens'] / max(1, st['steps']):.2f} tokens per step, a draft matched in {st['matched']} steps")
+        return out
     if sp is not None:
         lp = {}
         out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist(), lp_out=lp)
@@ -147,6 +184,37 @@ def print_logprobs(tok, out: list, lp: dict) -> None:
         alts = "  ".join(f"{j}:{v:.3f}" for j, v in lp["top"][i])
         print(f"  {t:>7d} {tok.decode([t])!r:<16} logprob {lp['lp'][i]:10.4f}  rank {lp['rank'][i]}"
               + (f"  top [{alts}]" if alts else ""))
+
+
+def speculative_tokens(eng, h, ids: list, n_new: int, k: int, ngram: tuple, sp, eos_ids) -> tuple:
+    """Speculative continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
+    hidden): the first token from the head (``Sampler.sample`` when sampling), the rest from a
+    captured ``SpecDecodeGraph`` on the GPU (the eager twin on the CPU), replayed until the sequence
+    is done. Returns (tokens, seconds, {steps, tokens, matched})."""
+    from llm_sharding_amd.runtime.sampling import Sampler
+    from llm_sharding_amd.runtime.speculative import EagerSpecDecode, SpecDecodeGraph
+    if sp is None:
+        first = eng.head(h, [len(ids) - 1])
+    else:
+        print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
+        first = Sampler(eng).sample(h, [len(ids) - 1], [sp], [len(ids)])
+    t1 = time.perf_counter()
+    g = (SpecDecodeGraph if eng.gpu else EagerSpecDecode)(eng, 1, k, ngram=ngram, sampling=sp is not None,
+                                                          history_len=max(1, n_new), eos_ids=eos_ids)
+    try:
+        g.admit(0, ids + [int(first[0])], n_new, sp)
+    except ValueError as e:
+        raise SystemExit(f"[ERROR] {e}")
+    g.capture()
+    left = n_new - 1
+    while left > 0 and not g.all_done():  # the fewest steps that can finish, then one look at the device
+        for _ in range(-(-left // (k + 1))):
+            g.replay()
+        r = g.results()[0]
+        left = n_new - len(r["tokens"])
+    dt_s = time.perf_counter() - t1
+    r = g.results()[0]
+    return r["tokens"], dt_s, {"steps": len(r["accepted"]), "tokens": sum(r["accepted"]), "matched": r["matched"]}
 
 
 def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out=None) -> tuple:
