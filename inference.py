@@ -10,6 +10,10 @@ or without a temperature (temperature 0: the arg-max of the penalised logits).
 ``--logprobs N`` (0..20) prints each generated token's log-probability, rank and N most likely
 alternatives (of the penalised logits at temperature 1, before top-k / top-p); ``--score`` prints the
 prompt's own per-token log-probabilities, mean NLL and perplexity instead of generating.
+``--logit-bias ID:VAL`` and ``--ban ID`` (both repeatable), ``--min-tokens N``, ``--min-p P`` and
+``--choice TEXT`` (repeatable: the output is exactly one of the texts' token sequences, then EOS)
+constrain the output on the device (``ops.constraints``); not together with ``--speculative``,
+``--score`` or ``--hf-compare``.
 ``--speculative K [--spec-ngram MIN,MAX]`` decodes speculatively: K tokens drafted from the sequence's
 own history (the longest n-gram match of MIN..MAX tokens) are verified in one step of K + 1 rows; the
 output is the plain output, greedy or sampled, in fewer steps when the text repeats itself.
@@ -21,6 +25,8 @@ output is the plain output, greedy or sampled, in fewer steps when the text repe
     python inference.py --random llama2-7b --repetition-penalty 1.2
     python inference.py --shards DIR --logprobs 5
     python inference.py --shards DIR --score --prompt "..."
+    python inference.py --shards DIR --choice " yes" --choice " no" --choice " maybe"
+    python inference.py --shards DIR --temperature 0.8 --min-p 0.05 --min-tokens 16 --ban 13
     python inference.py --shards DIR --speculative 3 [--temperature 0.7 --top-p 0.9 --seed 1]
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
@@ -64,6 +70,17 @@ def build_parser() -> argparse.ArgumentParser:
                     help="print each generated token's log-probability, rank and N (0..20) alternatives")
     ap.add_argument("--score", action="store_true",
                     help="score the prompt instead of generating: per-token log-probabilities, mean NLL, perplexity")
+    ap.add_argument("--logit-bias", action="append", default=[], metavar="ID:VAL",
+                    help="add VAL (finite, or -inf) to token ID's logit; repeatable")
+    ap.add_argument("--ban", action="append", type=int, default=[], metavar="ID",
+                    help="never produce token ID; repeatable")
+    ap.add_argument("--min-tokens", type=int, default=0, help="no EOS before this many generated tokens (0: off)")
+    ap.add_argument("--min-p", type=float, default=None,
+                    help="drop tokens with p < min_p * p_max at the temperature in use (HF's min_p; needs a "
+                         "temperature)")
+    ap.add_argument("--choice", action="append", default=[], metavar="TEXT",
+                    help="the output is exactly one of the given texts (tokenised without special tokens), then EOS; "
+                         "repeatable")
     ap.add_argument("--speculative", type=int, default=0, metavar="K",
                     help="speculative decoding: verify K (1..15) n-gram drafts per step (0: off)")
     ap.add_argument("--spec-ngram", default="1,3", metavar="MIN,MAX",
@@ -90,18 +107,38 @@ def speculative_from_args(a, sp):
     if sp is not None and (sp.penalized or sp.logprobs is not None):
         raise SystemExit("[ERROR] --speculative does not combine with the penalty flags or --logprobs "
                          "(their state is sequential per token)")
+    if constraint_flags(a):
+        raise SystemExit("[ERROR] --speculative does not combine with --logit-bias, --ban, --min-tokens, --min-p or "
+                         "--choice (the constraint state is sequential per token)")
     return a.speculative, (nmin, nmax)
 
 
-def sampling_from_args(a):
+def constraint_flags(a) -> bool:
+    return bool(a.logit_bias or a.ban or a.min_tokens or a.min_p is not None or a.choice)
+
+
+def sampling_from_args(a, choices=None):
     """The run's SamplingParams; None for the greedy default (temperature 0, no penalty, no
-    logprobs)."""
+    logprobs, no constraint). ``choices``: the token sequences of ``--choice``."""
     from llm_sharding_amd.runtime.sampling import SamplingParams
     pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
     if (a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0)
-            and a.logprobs is None):
+            and a.logprobs is None and not constraint_flags(a)):
         return None
-    sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen, logprobs=a.logprobs)
+    bias = {}
+    for item in a.logit_bias:
+        k, sep, v = item.partition(":")
+        try:
+            bias[int(k)] = float(v)
+        except ValueError:
+            raise SystemExit(f"[ERROR] --logit-bias takes ID:VAL, got {item!r}")
+    try:
+        sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen, logprobs=a.logprobs, logit_bias=bias or None,
+                            banned_token_ids=a.ban or None, min_tokens=a.min_tokens, min_p=a.min_p, choices=choices)
+    except ValueError as e:
+        if constraint_flags(a):
+            raise SystemExit(f"[ERROR] {e}")
+        raise
     return None if sp.plain else sp
 
 
@@ -111,6 +148,9 @@ def main(argv=None):
     spec = speculative_from_args(a, sp)
     if sp is not None and a.hf_compare:
         raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling and penalty flags")
+    if constraint_flags(a) and (a.score or a.hf_compare):
+        raise SystemExit("[ERROR] --score and --hf-compare do not combine with --logit-bias, --ban, --min-tokens, "
+                         "--min-p or --choice")
     if a.shards:
         cfg = LlamaConfig.from_pretrained(a.shards)
         src, tok = ShardFolderSource(a.shards, cfg), load_tokenizer(a.shards)
@@ -122,6 +162,8 @@ def main(argv=None):
     eng = StageEngine(cfg, 0, cfg.num_hidden_layers, a.device, dt, has_embed=True, has_head=True, source=src,
                       max_seq=min(cfg.max_position_embeddings, 4096))
     ids = tok(a.prompt, return_tensors="pt")["input_ids"][0]
+    if a.choice:
+        sp = sampling_from_args(a, [tok.encode(c, add_special_tokens=False) for c in a.choice])
     print(f"[INFO] loaded in {time.perf_counter() - t0:.1f}s; prompt tokens {ids.numel()}")
     if a.score:
         return score(eng, tok, ids.tolist())
@@ -221,10 +263,12 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out
     """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from ``Sampler.sample``, the rest from a captured
     ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
-    sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along. With
+    sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along, with a
+    constraint its ``ConstraintState``. With
     ``sp.logprobs`` the tokens' log-probabilities, ranks and alternatives go into the dict
     ``lp_out`` (``lp``, ``rank``, ``top``: per token a list of (id, logprob))."""
-    from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, PenaltyState, Sampler, SamplingDecodeGraph
+    from llm_sharding_amd.runtime.sampling import (ConstraintState, EagerSamplingDecode, PenaltyState, Sampler,
+                                                   SamplingDecodeGraph)
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
     pen, kw = None, {}
     if sp.penalized:
@@ -233,9 +277,20 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out
         pen = PenaltyState(eng, 1)
         pen.admit(0, prompt_ids)
         kw = {"penalties": pen}
+    con = None
+    if sp.constrained:
+        try:
+            con = ConstraintState(eng, 1, state_rows=max(1, sum(len(c) for c in sp.choices or ()) + 2))
+            con.admit(0, sp, n_prompt)
+        except ValueError as e:
+            raise SystemExit(f"[ERROR] {e}")
+        print(f"[INFO] constraints: {len(sp.bias_entries())} bias entries, min_tokens {sp.min_tokens}, "
+              f"min_p {sp.min_p}, {len(sp.choices or ())} choices")
+        kw["constraints"] = con
     want_lp = sp.logprobs is not None
-    first = Sampler(eng, pen).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if pen is not None else None,
-                                     return_logprobs=want_lp)
+    first = Sampler(eng, pen, con).sample(h, [n_prompt - 1], [sp], [n_prompt],
+                                          slots=[0] if pen is not None or con is not None else None,
+                                          return_logprobs=want_lp)
     steps = []
     if want_lp:
         first, lp0 = first

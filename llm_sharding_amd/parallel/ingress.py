@@ -122,7 +122,10 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     when none is given; optional ``repetition_penalty``, ``presence_penalty``,
     ``frequency_penalty``: penalties on repeated tokens, with or without a temperature; optional
     ``logprobs`` (0..20): per-token log-probabilities, ranks and that many alternatives in the
-    reply; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
+    reply; optional ``logit_bias`` (token id, as a string or an integer, -> bias),
+    ``banned_token_ids``, ``min_tokens``, ``min_p``, ``allowed_token_ids`` and ``choices`` (a list
+    of token-id sequences): constrained decoding, refused with an error reply when a field is
+    invalid or the automaton does not fit the server's arena; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
     optional ``n > 1``: that many samples of each prompt sharing one prefill, answered with a
     ``"choices"`` list - needs a server with ``prefix_slots``). Returns the number of requests
     queued."""
@@ -139,7 +142,8 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     n = 0
     for ids in rows:
         try:
-            # optional temperature / top_k / top_p / seed / *_penalty / logprobs keys; absent: greedy (the plain call)
+            # optional temperature / top_k / top_p / seed / *_penalty / logprobs / constraint keys; absent: greedy
+            # (the plain call)
             sp = SamplingParams.from_dict(msg)
             kw = {} if sp is None else {"sampling": sp}
             if samples != 1:

@@ -94,6 +94,7 @@ class Request:
     group: Optional[dict] = None  # submit_n: the state its children share
     entry: Optional["_PoolEntry"] = None  # FORKING: the pool entry it forks from ...
     fork_len: int = 0  # ... and how many tokens
+    constraint: Optional[object] = None  # sampling.constrained: its CompiledConstraint (automaton acquired)
 
     @property
     def ttft_ms(self) -> float:
@@ -159,7 +160,7 @@ class PipelineServer:
                  device="cpu", batch: int = 8, microbatches: int = 1, max_seq: int = 2048,
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
                  ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
-                 prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH):
+                 prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256):
         self.cfg, self.rank, self.world = cfg, rank, world
         # prefix pool: engine slots >= B * M, never decoded, in no micro-batch and no graph
         self.P = int(prefix_slots)
@@ -204,6 +205,12 @@ class PipelineServer:
         self.penalties = None
         # logprobs: the graphs carry the lsa_logprobs launch from the first request that asks on
         self.logprobs_on = False
+        # constraints: the automaton arena (state_rows rows) and the per-slot tables exist, and the
+        # graphs carry the lsa_logit_process launch, from the first constrained request on; the
+        # host allocator of the arena's rows from the first constrained submit on
+        self.state_rows = int(state_rows)
+        self.constraints = None
+        self._arena = None
         self._lp_out: List = [None] * microbatches  # logprobs of a micro-batch's outstanding command
         self._build_graphs()
         # rank 0 state
@@ -241,14 +248,15 @@ class PipelineServer:
                 if self.sampling_on:
                     from ..runtime.sampling import SamplingDecodeGraph
                     g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S,
-                                            penalties=self.penalties, logprobs=self.logprobs_on)
+                                            penalties=self.penalties, logprobs=self.logprobs_on,
+                                            constraints=self.constraints)
                 else:
                     g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
                 self.graphs.append(g.capture())
         for st in self.streams:  # after weight loading and graph capture on the current stream
             st.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _enable_sampling(self, penalties: bool = False, logprobs: bool = False) -> None:
+    def _enable_sampling(self, penalties: bool = False, logprobs: bool = False, constraints: bool = False) -> None:
         """First non-greedy request (world == 1): build the Sampler and, in graph mode, replace
         every micro-batch's greedy graph by a SamplingDecodeGraph that takes over its device
         positions and tokens. Rows start greedy; a slot's parameters are written on admission.
@@ -257,9 +265,28 @@ class PipelineServer:
         from ..runtime.sampling import PenaltyState, Sampler
         if penalties:  # the first non-greedy request is a penalised one: one rebuild for both
             self.penalties = PenaltyState(self.eng, self.B * self.M)
+        if constraints:
+            self.constraints = self._new_constraints()
         self.logprobs_on = self.logprobs_on or logprobs
-        self.sampler = Sampler(self.eng, self.penalties)
+        self.sampler = Sampler(self.eng, self.penalties, self.constraints)
         self.sampling_on = True
+        self._swap_sampling_graphs()
+
+    def _new_constraints(self):
+        from ..ops.constraints import ArenaAllocator
+        from ..runtime.sampling import ConstraintState
+        with self._lock:
+            if self._arena is None:
+                self._arena = ArenaAllocator(self.state_rows)
+        return ConstraintState(self.eng, self.B * self.M, self.state_rows, allocator=self._arena)
+
+    def _enable_constraints(self) -> None:
+        """First constrained request (sampling already on): allocate the ConstraintState and, in
+        graph mode, replace every sampling graph by one whose step runs ``lsa_logit_process``
+        between ``lsa_penalize`` and ``lsa_sample``, carrying positions, tokens and the rows'
+        parameters over. Until then no graph holds that kernel and no table is allocated."""
+        self.constraints = self._new_constraints()
+        self.sampler.constraints = self.constraints
         self._swap_sampling_graphs()
 
     def _enable_penalties(self) -> None:
@@ -288,7 +315,8 @@ class PipelineServer:
         old, self.graphs = self.graphs, []
         for mb in range(self.M):
             g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S,
-                                    penalties=self.penalties, logprobs=self.logprobs_on)
+                                    penalties=self.penalties, logprobs=self.logprobs_on,
+                                    constraints=self.constraints)
             g.pos.copy_(old[mb].pos)
             g.tokens.copy_(old[mb].tokens)
             for i, p in enumerate(getattr(old[mb], "params", ())):
@@ -310,7 +338,7 @@ class PipelineServer:
         sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
         if sel:
             pen = {}
-            if self.penalties is not None:
+            if self.penalties is not None or self.constraints is not None:
                 pen = {"slots": [slots[i] for i in sel],
                        "tokens_in": None if tokens_in is None else [tokens_in[i] for i in sel]}
             want_lp = self.logprobs_on and any(reqs[i].sampling.logprobs is not None for i in sel)
@@ -370,7 +398,12 @@ class PipelineServer:
                     if self.gpu:
                         torch.cuda.empty_cache()
                     self.penalties = PenaltyState(self.eng, self.B * self.M)
-                self.sampler = Sampler(self.eng, self.penalties)
+                if self.constraints is not None:  # drained: no slot holds an automaton; waiting requests
+                    self.constraints = None       # keep their references in the allocator
+                    if self.gpu:
+                        torch.cuda.empty_cache()
+                    self.constraints = self._new_constraints()
+                self.sampler = Sampler(self.eng, self.penalties, self.constraints)
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
@@ -515,6 +548,12 @@ class PipelineServer:
                             r = self.by_slot.get(s)
                             if r is not None and r.sampling is not None and r.sampling.penalized:
                                 self.penalties.admit(s, r.input_ids)
+                    if self.constraints is not None:  # a constrained request enters its slot
+                        for (s, _, _, _) in em:
+                            r = self.by_slot.get(s)
+                            if r is not None and r.constraint is not None:
+                                self.constraints.admit(s, r.sampling, len(r.input_ids), compiled=r.constraint,
+                                                       acquired=True)
                     tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok,
                                             mb=mb)
                     if self.graph_mode:  # the slot's parameters, before its first decode step
@@ -579,8 +618,11 @@ class PipelineServer:
         a pool slot once and forked from there by this and later requests (``L`` is clamped to
         ``len - 1``: the last prompt token is always computed). ``sampling``:
         temperature / top-k / top-p / seed, repetition / presence / frequency penalties and
-        ``logprobs`` of the request (None, or temperature 0 with every penalty off and no logprobs:
-        greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
+        ``logprobs`` of the request, and its constraint fields (``logit_bias``, ``banned_token_ids``,
+        ``min_tokens``, ``min_p``, ``allowed_token_ids``, ``choices``, ``automaton``: checked here
+        against the vocabulary, and the automaton's rows of the arena are reserved here - ValueError
+        when they do not fit) (None, or temperature 0 with every penalty off, no logprobs and no
+        constraint: greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
         batch it runs in. With ``logprobs`` the finished :class:`Request` holds ``token_logprobs``,
         ``ranks`` and (``logprobs >= 1``) ``top_logprobs``, one entry per generated token."""
         if not self.first:
@@ -596,6 +638,17 @@ class PipelineServer:
         if len(ids) + max_new_tokens > self.eng.max_seq:
             raise ValueError(f"prompt ({len(ids)}) + max_new_tokens ({max_new_tokens}) exceeds max_seq "
                              f"{self.eng.max_seq}")
+        constraint = None
+        if sampling is not None and sampling.constrained:
+            from ..ops.constraints import ArenaAllocator
+            from ..runtime.sampling import _check_full_head, compile_constraints
+            _check_full_head(self.eng)
+            constraint = compile_constraints(sampling, self.cfg.vocab_size, self.cfg.eos_ids)
+            if constraint.automaton is not None:  # its rows of the arena, now: no room is an error now
+                with self._lock:
+                    if self._arena is None:
+                        self._arena = ArenaAllocator(self.state_rows)
+                    self._arena.acquire(constraint.automaton)
         with self._lock:
             rid = self._next_id
             self._next_id += 1
@@ -603,7 +656,7 @@ class PipelineServer:
         if cache_prefix is not None:
             cache_prefix = max(0, min(int(cache_prefix), len(ids) - 1))
         r = Request(rid, ids, int(max_new_tokens), eos, on_token=on_token, reply_to=reply_to, sampling=sampling,
-                    t_submit=time.perf_counter(), cache_prefix=cache_prefix, group=_group)
+                    t_submit=time.perf_counter(), cache_prefix=cache_prefix, group=_group, constraint=constraint)
         self.incoming.put(r)
         return rid
 
@@ -755,6 +808,8 @@ class PipelineServer:
             r.on_token(r, tok)
         if tok in r.eos_ids or len(r.output_ids) >= r.max_new_tokens:
             r.state, r.t_done = DONE, now
+            if r.constraint is not None and self.constraints is not None:
+                self.constraints.release(r.slot)
             mb = r.slot // self.B
             del self.by_slot[r.slot]
             self.cur_tok.pop(r.slot, None)
@@ -828,7 +883,10 @@ class PipelineServer:
                 break
             r = self.waiting.pop(0)
             if r.sampling is not None and not self.sampling_on:
-                self._enable_sampling(penalties=r.sampling.penalized, logprobs=r.sampling.logprobs is not None)
+                self._enable_sampling(penalties=r.sampling.penalized, logprobs=r.sampling.logprobs is not None,
+                                      constraints=r.constraint is not None)
+            if r.constraint is not None and self.constraints is None:
+                self._enable_constraints()
             if r.sampling is not None and r.sampling.penalized and self.penalties is None:
                 self._enable_penalties()
             if r.sampling is not None and r.sampling.logprobs is not None and not self.logprobs_on:

@@ -14,6 +14,10 @@ path that exists only when a request asks for it.
 * :class:`PenaltyState` - the per-slot token statistics of the repetition / presence / frequency
   penalties (``ops.penalties``); it exists only once a request asks for a penalty, and a graph or
   Sampler built without it runs exactly the code above.
+* :class:`ConstraintState` - the automaton arena and the per-slot tables of constrained decoding
+  (``ops.constraints``: logit bias, banned tokens, ``min_tokens``, min-p, token automata); it
+  exists only once a request asks for one of them, and a graph or Sampler built without it runs
+  exactly the code above. The order is penalise -> process -> sample -> logprobs.
 * Log-probabilities (``SamplingParams.logprobs``, ``ops.logprobs``): :meth:`Sampler.logprobs`,
   ``SamplingDecodeGraph(..., logprobs=True)`` (one ``lsa_logprobs`` launch behind
   ``argmax_finalize``; a graph built without it captures exactly the step above) and
@@ -25,13 +29,16 @@ function of seed, position and vocabulary index), not on the row, slot or batch 
 """
 from __future__ import annotations
 
+import math
 import numbers
 import os
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Any, Optional, Sequence
 
+import numpy as np
 import torch
 
+from ..ops import constraints as K
 from ..ops import logprobs as LP
 from ..ops import penalties as P
 from ..ops import sampling as S
@@ -48,7 +55,18 @@ class SamplingParams:
     draw - also at temperature 0, which then takes the arg-max of the penalised logits.
     ``logprobs`` (None = off): ``0`` returns the chosen token's log-probability and rank, ``1..20``
     also that many most likely alternatives - of the penalised logits at temperature 1, before the
-    top-k / top-p filters."""
+    top-k / top-p filters.
+
+    Constrained decoding (``ops.constraints``; every field off by default): ``logit_bias`` (token ->
+    a finite value or ``-inf``, added to the logit) and ``banned_token_ids`` (a bias of ``-inf``)
+    share 320 entries; ``min_tokens`` masks every EOS id of the configuration until that many
+    tokens have been generated; ``min_p`` in (0, 1] masks tokens with ``p_i < min_p * p_max`` at
+    the request's temperature (ignored at temperature 0); ``allowed_token_ids`` (only these tokens
+    - include EOS if the output may end), ``choices`` (the output is exactly one of these token-id
+    sequences, then EOS) and ``automaton`` (an explicit :class:`ops.constraints.TokenAutomaton`,
+    the hook of an external regex / grammar compiler) exclude one another, and ``banned_token_ids``,
+    a ``-inf`` bias and ``min_tokens``: the automaton decides what may appear and when the output
+    ends, so a row can never lose every column."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
@@ -57,8 +75,16 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logprobs: Optional[int] = None
+    logit_bias: Optional[dict] = None
+    banned_token_ids: Optional[list] = None
+    min_tokens: int = 0
+    min_p: Optional[float] = None
+    allowed_token_ids: Optional[list] = None
+    choices: Optional[list] = None
+    automaton: Optional[Any] = None
 
     def __post_init__(self):
+        self._check_constraints()
         self.temperature, self.top_k, self.top_p = float(self.temperature), int(self.top_k), float(self.top_p)
         if not self.temperature >= 0.0 or self.temperature == float("inf"):
             raise ValueError(f"temperature must be a finite value >= 0, got {self.temperature}")
@@ -92,10 +118,84 @@ class SamplingParams:
     def penalized(self) -> bool:
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
 
+    def _check_constraints(self) -> None:
+        """The checks of the constraint fields that need no vocabulary (``compile_constraints``
+        does the rest against a configuration)."""
+        def ids(x, what):
+            if isinstance(x, (str, bytes)) or not hasattr(x, "__iter__"):
+                raise ValueError(f"{what} must be a list of token ids, got {x!r}")
+            out = []
+            for t in x:
+                if isinstance(t, bool) or not isinstance(t, numbers.Integral) or t < 0:
+                    raise ValueError(f"{what}: token ids are integers >= 0, got {t!r}")
+                out.append(int(t))
+            return out
+
+        if self.logit_bias is not None:
+            if not isinstance(self.logit_bias, dict):
+                raise ValueError(f"logit_bias must be a dict of token id -> bias, got {self.logit_bias!r}")
+            lb = {}
+            for k, v in self.logit_bias.items():
+                try:
+                    t, b = int(k), float(v)
+                except (TypeError, ValueError):
+                    raise ValueError(f"logit_bias: token id -> number, got {k!r}: {v!r}") from None
+                if t < 0 or isinstance(k, (bool, float)):
+                    raise ValueError(f"logit_bias: token ids are integers >= 0, got {k!r}")
+                if math.isnan(b) or b == float("inf"):
+                    raise ValueError(f"logit_bias[{t}] must be finite or -inf, got {b}")
+                lb[t] = b
+            self.logit_bias = lb or None
+        if self.banned_token_ids is not None:
+            self.banned_token_ids = sorted(set(ids(self.banned_token_ids, "banned_token_ids"))) or None
+        if len(self.bias_entries()) > K.BIAS_MAX:
+            raise ValueError(f"logit_bias and banned_token_ids together hold {len(self.bias_entries())} entries, more "
+                             f"than {K.BIAS_MAX}")
+        mt = self.min_tokens
+        if isinstance(mt, bool) or not isinstance(mt, numbers.Integral) or not 0 <= mt < 1 << 30:
+            raise ValueError(f"min_tokens must be an integer >= 0, got {mt!r}")
+        self.min_tokens = int(mt)
+        if self.min_p is not None:
+            self.min_p = float(self.min_p)
+            if not 0.0 < self.min_p <= 1.0:
+                raise ValueError(f"min_p must be in (0, 1], got {self.min_p}")
+        if self.allowed_token_ids is not None:
+            self.allowed_token_ids = sorted(set(ids(self.allowed_token_ids, "allowed_token_ids")))
+            if not self.allowed_token_ids:
+                raise ValueError("allowed_token_ids: at least one token")
+        if self.choices is not None:
+            if isinstance(self.choices, (str, bytes)) or not hasattr(self.choices, "__iter__"):
+                raise ValueError("choices must be a list of token-id sequences")
+            self.choices = [ids(c, "choices") for c in self.choices]
+            if not self.choices or any(not c for c in self.choices):
+                raise ValueError("choices: at least one choice, and no empty choice")
+        if self.automaton is not None and not isinstance(self.automaton, K.TokenAutomaton):
+            raise ValueError("automaton must be an ops.constraints.TokenAutomaton")
+        kinds = [k for k in ("allowed_token_ids", "choices", "automaton") if getattr(self, k) is not None]
+        if len(kinds) > 1:
+            raise ValueError(f"at most one of allowed_token_ids / choices / automaton, got {kinds}")
+        if kinds and (self.min_tokens or any(b == float("-inf") for _, b in self.bias_entries())):
+            raise ValueError(f"{kinds[0]} cannot be combined with banned_token_ids, a -inf bias or min_tokens: the "
+                             "automaton decides what may appear and when the output ends")
+
+    def bias_entries(self) -> list:
+        """``[(token, bias)]`` of ``logit_bias`` and ``banned_token_ids`` (``-inf``; a ban wins),
+        distinct tokens in ascending order."""
+        e = dict(self.logit_bias or {})
+        e.update({int(t): float("-inf") for t in self.banned_token_ids or ()})
+        return sorted(e.items())
+
+    @property
+    def constrained(self) -> bool:
+        """Any constraint field is on: the request needs a :class:`ConstraintState`."""
+        return bool(self.logit_bias or self.banned_token_ids or self.min_tokens or self.min_p is not None
+                    or self.allowed_token_ids is not None or self.choices is not None or self.automaton is not None)
+
     @property
     def plain(self) -> bool:
-        """Needs no sampling path at all: temperature 0, every penalty off, no logprobs."""
-        return self.greedy and not self.penalized and self.logprobs is None
+        """Needs no sampling path at all: temperature 0, every penalty off, no logprobs, no
+        constraint."""
+        return self.greedy and not self.penalized and self.logprobs is None and not self.constrained
 
     @property
     def n_top(self) -> int:
@@ -105,10 +205,11 @@ class SamplingParams:
     @classmethod
     def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
         """``temperature / top_k / top_p / seed / repetition_penalty / presence_penalty /
-        frequency_penalty / logprobs`` keys of a request dict; None (greedy) when none of them is
-        present."""
+        frequency_penalty / logprobs / logit_bias / banned_token_ids / min_tokens / min_p /
+        allowed_token_ids / choices`` keys of a request dict (``logit_bias`` with string or integer
+        keys); None (greedy) when none of them is present."""
         keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty",
-                "logprobs")
+                "logprobs", "logit_bias", "banned_token_ids", "min_tokens", "min_p", "allowed_token_ids", "choices")
         if not any(d.get(k) is not None for k in keys):
             return None
         return cls(**{k: d[k] for k in keys if d.get(k) is not None})
@@ -175,14 +276,158 @@ class PenaltyState:
         return logits
 
 
+@dataclass
+class CompiledConstraint:
+    """One request's constraint fields against a configuration: what :meth:`ConstraintState.admit`
+    writes into a slot."""
+    automaton: Optional[K.TokenAutomaton]
+    bias_tok: list
+    bias_val: list
+    min_tokens: int
+    minp_delta: float  # float32(T * ln(min_p)); -inf = off
+
+
+def compile_constraints(params: SamplingParams, vocab_size: int, eos_ids) -> CompiledConstraint:
+    """The checks of ``params``' constraint fields that need the vocabulary and the EOS ids
+    (ValueError), the automaton of ``allowed_token_ids`` / ``choices``, and ``minp_delta``."""
+    V, eos = int(vocab_size), [int(e) for e in eos_ids or ()]
+    if len(eos) > K.N_EOS:
+        raise ValueError(f"constraints: at most {K.N_EOS} EOS ids, the configuration has {len(eos)}")
+    entries = params.bias_entries()
+    if any(t >= V for t, _ in entries):
+        raise ValueError(f"logit_bias / banned_token_ids: token outside the vocabulary [0, {V})")
+    auto = params.automaton
+    if params.allowed_token_ids is not None:
+        auto = K.TokenAutomaton.from_allowed(params.allowed_token_ids, V)
+    elif params.choices is not None:
+        auto = K.TokenAutomaton.from_choices(params.choices, V, eos)
+    elif auto is not None and auto.vocab != V:
+        raise ValueError(f"automaton: a table over {auto.vocab} tokens for a vocabulary of {V}")
+    if auto is None:
+        gone = {t for t, b in entries if b == float("-inf")} | set(eos if params.min_tokens else ())
+        if len(gone) >= V:
+            raise ValueError("banned_token_ids and the EOS ids cover the whole vocabulary")
+    delta = float("-inf")
+    if params.min_p is not None and params.temperature > 0.0:
+        delta = float(np.float32(params.temperature * math.log(params.min_p)))
+    return CompiledConstraint(auto, [t for t, _ in entries], [b for _, b in entries], params.min_tokens, delta)
+
+
+class ConstraintState:
+    """The tables of constrained decoding (``ops.constraints``) on the engine's device: the
+    automaton arena ``int16 [state_rows, head_rows]`` (one row per automaton state - 256 rows are
+    16 MB at a vocabulary of 32000 and 66 MB at 128256), the per-slot rows ``astate / abase / bias_n
+    / bias_tok / bias_val / min_until / minp_delta / fault`` and the configuration's EOS ids. Built
+    when the first constrained request arrives. ``allocator`` (an :class:`ops.constraints.ArenaAllocator`
+    of ``state_rows`` rows, by default a new one) places automata in contiguous row ranges and
+    shares them by content digest; an automaton's rows are uploaded when its first request is
+    admitted."""
+
+    def __init__(self, eng: StageEngine, n_slots: int, state_rows: int = 256,
+                 allocator: Optional[K.ArenaAllocator] = None):
+        _check_full_head(eng)
+        self.eng, self.n_slots, self.state_rows = eng, int(n_slots), int(state_rows)
+        self.alloc = K.ArenaAllocator(self.state_rows) if allocator is None else allocator
+        if self.alloc.state_rows != self.state_rows or self.n_slots < 1:
+            raise ValueError("ConstraintState: the allocator must cover state_rows rows, and n_slots >= 1")
+        dev, n = eng.device, self.n_slots
+        self.arena = torch.full((self.state_rows, eng.cfg.head_rows), -1, dtype=torch.int16, device=dev)
+        self.astate = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.abase = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.bias_n = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.bias_tok = torch.zeros((n, K.BIAS_MAX), dtype=torch.int32, device=dev)
+        self.bias_val = torch.zeros((n, K.BIAS_MAX), dtype=torch.float32, device=dev)
+        self.min_until = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.minp_delta = torch.full((n,), float("-inf"), dtype=torch.float32, device=dev)
+        self.fault = torch.zeros(n, dtype=torch.int32, device=dev)
+        eos = [int(e) for e in eng.cfg.eos_ids][:K.N_EOS]
+        self.eos = torch.tensor(eos + [-1] * (K.N_EOS - len(eos)), dtype=torch.int32, device=dev)
+        self.resident: set = set()      # digests whose rows are in the arena
+        self.held: dict = {}            # slot -> digest of the automaton it holds
+
+    def compile(self, params: SamplingParams) -> CompiledConstraint:
+        return compile_constraints(params, self.eng.cfg.vocab_size, self.eng.cfg.eos_ids)
+
+    def admit(self, slot: int, params: Optional[SamplingParams], prompt_len: int,
+              compiled: Optional[CompiledConstraint] = None, acquired: bool = False) -> None:
+        """A request enters ``slot``: write its rows and point ``astate`` at its automaton's start
+        state. ``compiled`` / ``acquired``: the caller has compiled the fields, and already holds
+        the allocator's reference (the server does both when the request is submitted)."""
+        if not 0 <= slot < self.n_slots:
+            raise ValueError(f"slot {slot} outside the constraint tables of {self.n_slots}")
+        self.release(slot)
+        if params is None or not params.constrained:
+            return
+        c = self.compile(params) if compiled is None else compiled
+        base = -1
+        if c.automaton is not None:
+            d = c.automaton.digest
+            base = self.alloc.base(d) if acquired else self.alloc.acquire(c.automaton)
+            self.held[slot] = d
+            if d not in self.resident:
+                rows = torch.from_numpy(np.array(c.automaton.next)).to(self.arena.device)
+                self.arena[base:base + c.automaton.n_states, :c.automaton.vocab] = rows
+                if self.eng.gpu:  # streams other than this one may admit the same automaton next
+                    torch.cuda.current_stream(self.arena.device).synchronize()
+                self.resident.add(d)
+        n = len(c.bias_tok)
+        self.abase[slot] = max(base, 0)
+        self.astate[slot] = base
+        self.bias_n[slot] = n
+        if n:
+            dev = self.bias_tok.device
+            self.bias_tok[slot, :n] = torch.tensor(c.bias_tok, dtype=torch.int32, device=dev)
+            self.bias_val[slot, :n] = torch.tensor(c.bias_val, dtype=torch.float32, device=dev)
+        self.min_until[slot] = int(prompt_len) + c.min_tokens if c.min_tokens else 0
+        self.minp_delta[slot] = c.minp_delta
+        self.fault[slot] = 0
+
+    def release(self, slot: int) -> None:
+        """Clear ``slot``; the automaton it held loses one reference (``fault`` stays readable
+        until the next :meth:`admit`)."""
+        d = self.held.pop(slot, None)
+        if d is not None and self.alloc.release(d):
+            self.resident.discard(d)
+        self.astate[slot] = -1
+        self.bias_n[slot] = 0
+        self.min_until[slot] = 0
+        self.minp_delta[slot] = float("-inf")
+
+    def apply(self, logits: torch.Tensor, slots, tokens_in, positions) -> torch.Tensor:
+        """Advance ``slots[i]`` by ``tokens_in[i]`` (None: nothing) and process row i of bf16
+        ``logits`` [n, >= vocab_size]; ``positions[i]`` is the position the sampled token will
+        occupy. ``lsa_logit_process`` in place on the GPU, the numpy reference on a CPU engine.
+        Returns the processed logits."""
+        n, V = logits.shape[0], self.eng.cfg.vocab_size
+        slots = [int(s) for s in slots]
+        positions = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
+        if len(slots) != n or len(positions) != n or (tokens_in is not None and len(tokens_in) != n):
+            raise ValueError(f"constraints: {n} rows, {len(slots)} slots, {len(positions)} positions")
+        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
+            raise ValueError(f"constraints: slots {slots} must be distinct and below {self.n_slots}")
+        if not self.eng.gpu:
+            out, ast, flt = K.logit_process_reference(logits.to(torch.bfloat16), V, self, slots, tokens_in, positions)
+            self.astate.copy_(torch.from_numpy(ast))
+            self.fault.copy_(torch.from_numpy(flt))
+            return out
+        dev = self.eng.device
+        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
+        K.logit_process(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin,
+                        torch.tensor(positions, dtype=torch.int32, device=dev), self)
+        return logits
+
+
 class Sampler:
     """Logits and sampled tokens of a stage that holds the whole lm_head. ``penalties``: the
-    stage's :class:`PenaltyState`, applied by :meth:`sample` to the rows given ``slots``."""
+    stage's :class:`PenaltyState`, applied by :meth:`sample` to the rows given ``slots``;
+    ``constraints``: its :class:`ConstraintState`, applied behind the penalties."""
 
-    def __init__(self, eng: StageEngine, penalties: Optional[PenaltyState] = None):
+    def __init__(self, eng: StageEngine, penalties: Optional[PenaltyState] = None,
+                 constraints: Optional[ConstraintState] = None):
         _check_full_head(eng)
         self.eng = eng
         self.penalties = penalties
+        self.constraints = constraints
 
     # ------------------------------------------------------------------ logits
     def logits(self, h: torch.Tensor, rows_idx=None) -> torch.Tensor:
@@ -304,7 +549,10 @@ class Sampler:
         token after a prefill uses ``positions[i]`` = the prompt length. ``slots`` (with a
         :class:`PenaltyState`): row i belongs to sequence slot ``slots[i]`` and is penalised by
         its parameters first; ``tokens_in[i]`` is the token the row's step was fed (counted as
-        generated) - None for the first token after a prefill, which only sees the prompt.
+        generated) - None for the first token after a prefill, which only sees the prompt. With a
+        :class:`ConstraintState` the rows of constrained requests are then processed
+        (``ops.constraints``: the automaton advances by ``tokens_in[i]``), in the order penalise ->
+        process -> sample -> logprobs.
         ``return_logprobs``: returns ``(tokens, Logprobs)`` - the log-probabilities of the sampled
         tokens under the (penalised) logits, for the rows whose parameters ask for them."""
         logits = self.logits(h, rows_idx)
@@ -312,6 +560,11 @@ class Sampler:
             if self.penalties is None or slots is None:
                 raise RuntimeError("a penalised request needs a PenaltyState (Sampler(eng, penalties=...)) and slots=")
             logits = self.penalties.apply(logits, slots, tokens_in, params_list)
+        if any(p.constrained for p in params_list):
+            if self.constraints is None or slots is None:
+                raise RuntimeError("a constrained request needs a ConstraintState (Sampler(eng, constraints=...)) and "
+                                   "slots=")
+            logits = self.constraints.apply(logits, slots, tokens_in, positions)
         tok = self.sample_logits(logits, params_list, positions)
         if not return_logprobs:
             return tok
@@ -348,14 +601,21 @@ class SamplingDecodeGraph(DecodeGraph):
     live on the device; with a token history, ``lp_history`` keeps ``tok_lp`` of the same steps
     (NaN where a row was skipped). Without it the captured step is exactly the one above.
 
+    With ``constraints`` (a :class:`ConstraintState` that covers this graph's slots) one
+    ``lsa_logit_process`` launch sits between ``lsa_penalize`` and ``lsa_sample``: it advances the
+    rows' automaton states by the step's input tokens and applies bias, EOS mask, automaton mask
+    and min-p from the per-slot device tables (written by :meth:`ConstraintState.admit`); rows
+    whose slots hold no constraint are skipped. The log-probabilities then describe the processed
+    row. Without it the captured step is exactly the one above.
+
     The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
                  history_len: int = 0, scratch: int = 0, penalties: Optional[PenaltyState] = None,
-                 debug_raw: bool = False, logprobs: bool = False):
+                 debug_raw: bool = False, logprobs: bool = False, constraints: Optional[ConstraintState] = None):
         if mode not in ("full", "last"):
             raise ValueError("SamplingDecodeGraph runs the head: mode 'full' or 'last'")
-        self.sampler = Sampler(eng, penalties)
+        self.sampler = Sampler(eng, penalties, constraints)
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len, scratch=scratch)
         dev = eng.device
         self.params = [GREEDY] * rows
@@ -370,6 +630,10 @@ class SamplingDecodeGraph(DecodeGraph):
             self.rep = torch.ones(rows, dtype=torch.float32, device=dev)
             self.pres = torch.zeros(rows, dtype=torch.float32, device=dev)
             self.freq = torch.zeros(rows, dtype=torch.float32, device=dev)
+        self.constraints = constraints
+        if constraints is not None:
+            if constraints.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= constraints.n_slots:
+                raise ValueError("constraints: a ConstraintState of this engine with a distinct row per graph slot")
         self.lp = self.n_top = self.lp_history = None
         if logprobs:
             self.n_top = torch.full((rows,), -1, dtype=torch.int32, device=dev)
@@ -384,6 +648,8 @@ class SamplingDecodeGraph(DecodeGraph):
             raise RuntimeError("a penalised request needs SamplingDecodeGraph(..., penalties=PenaltyState)")
         if p.logprobs is not None and self.lp is None:
             raise RuntimeError("a request with logprobs needs SamplingDecodeGraph(..., logprobs=True)")
+        if p.constrained and self.constraints is None:
+            raise RuntimeError("a constrained request needs SamplingDecodeGraph(..., constraints=ConstraintState)")
         self.params[row] = p
         self.temperature[row] = p.temperature
         self.top_k[row] = p.top_k
@@ -397,14 +663,20 @@ class SamplingDecodeGraph(DecodeGraph):
             self.n_top[row] = p.n_top
 
     def capture(self, warmup: bool = True) -> "SamplingDecodeGraph":
-        """The warm-up run counts tokens into the penalty state: the graph's rows are restored."""
+        """The warm-up run counts tokens into the penalty state and advances the automaton states:
+        the graph's rows are restored."""
+        cs = self.constraints
+        idx = self.slot.long()
+        kept = None if cs is None else (cs.astate.index_select(0, idx), cs.fault.index_select(0, idx))
         if self.penalties is None:
             super().capture(warmup)
         else:
-            idx = self.slot.long()
             saved = self.penalties.state.index_select(0, idx)
             super().capture(warmup)
             self.penalties.state.index_copy_(0, idx, saved)
+        if kept is not None:
+            cs.astate.index_copy_(0, idx, kept[0])
+            cs.fault.index_copy_(0, idx, kept[1])
         if self.lp_history is not None:
             self.lp_history.fill_(float("nan"))
         return self
@@ -423,6 +695,9 @@ class SamplingDecodeGraph(DecodeGraph):
         if self.penalties is not None:
             P.penalize(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.penalties.state,
                        self.rep, self.pres, self.freq)
+        if self.constraints is not None:
+            K.logit_process(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.pos, self.constraints,
+                            ctr_add=1)
         S.sample(self.logits, eng.cfg.vocab_size, rows, self.temperature, self.top_k, self.top_p, self.seed, self.pos,
                  self.keys, ctr_add=1)
         hip.argmax_finalize(self.keys, rows, self.tokens, self.pos, 1, self.history,
@@ -436,12 +711,14 @@ class EagerSamplingDecode(EagerDecode):
     """:class:`SamplingDecodeGraph`'s interface on devices without graphs (CPU engines)."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0,
-                 penalties: Optional[PenaltyState] = None, logprobs: bool = False):
+                 penalties: Optional[PenaltyState] = None, logprobs: bool = False,
+                 constraints: Optional[ConstraintState] = None):
         if mode not in ("full", "last"):
             raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
-        self.sampler = Sampler(eng, penalties)
+        self.sampler = Sampler(eng, penalties, constraints)
         self.penalties = penalties
+        self.constraints = constraints
         self.params = [GREEDY] * rows
         self.lp = self.lp_history = None
         if logprobs:
@@ -453,6 +730,8 @@ class EagerSamplingDecode(EagerDecode):
         p = GREEDY if params is None else params
         if p.logprobs is not None and self.lp is None:
             raise RuntimeError("a request with logprobs needs EagerSamplingDecode(..., logprobs=True)")
+        if p.constrained and self.constraints is None:
+            raise RuntimeError("a constrained request needs EagerSamplingDecode(..., constraints=ConstraintState)")
         self.params[row] = p
 
     def _body(self) -> None:
@@ -461,7 +740,9 @@ class EagerSamplingDecode(EagerDecode):
         slot, pos = eng.prefill_rows(self.slots, [1] * self.rows)
         h = eng.forward(h, slot, pos)
         eng.advance(self.slots, [1] * self.rows)
-        pen = {} if self.penalties is None else {"slots": self.slots, "tokens_in": self.tokens.tolist()}
+        pen = {}
+        if self.penalties is not None or self.constraints is not None:
+            pen = {"slots": self.slots, "tokens_in": self.tokens.tolist()}
         tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], return_logprobs=self.lp is not None,
                                   **pen)
         if self.lp is not None:
@@ -516,5 +797,6 @@ def score_prompt(eng: StageEngine, ids, top: int = 0, slot: int = 0):
     return LP.Logprobs(*(torch.cat([p[i] for p in parts]) for i in range(5)))
 
 
-__all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "SamplingDecodeGraph", "EagerSamplingDecode",
+__all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "ConstraintState", "CompiledConstraint",
+           "compile_constraints", "SamplingDecodeGraph", "EagerSamplingDecode",
            "device_params", "score_prompt", "SCORE_CHUNK_BYTES"]

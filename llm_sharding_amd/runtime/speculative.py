@@ -108,6 +108,10 @@ class _SpecState:
         if p.penalized or p.logprobs is not None:
             raise ValueError("speculative: penalties and logprobs are sequential per slot and not supported "
                              "together with speculation")
+        if p.constrained:
+            raise ValueError("speculative: constrained decoding (logit_bias, banned_token_ids, min_tokens, min_p, "
+                             "allowed_token_ids, choices, automaton) keeps sequential state per slot and is not "
+                             "supported together with speculation")
         if not p.greedy and not self.sampling:
             raise ValueError("speculative: a sampled sequence needs sampling=True")
         row = np.zeros(self.ld, dtype=np.int32)

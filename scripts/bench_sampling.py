@@ -22,9 +22,19 @@
    ``SamplingDecodeGraph`` (temperature 0.7, top-p 0.9) with ``logprobs=5`` against the same graph
    without, in alternating windows of one process.
 
+5. ``--constraints`` (results: profiles/logit_process.md) instead: ``lsa_logit_process`` alone at 1 and
+   512 rows of V = 32000 for 320 bias entries, an automaton (half the vocabulary allowed, a
+   different arena row per slot) and automaton + min-p (the row kept in registers, and re-read from
+   L2), 50 launches captured in one graph: once on
+   logits that already carry the masks (reads only) and once with the logits restored in front of
+   every launch (reads and writes; the restoring copy, captured alone, is subtracted), next to
+   ``lsa_penalize`` and ``lsa_sample`` from the same process; and the TPOT of a 7B-shaped
+   ``SamplingDecodeGraph`` whose rows decode under ``choices`` against the same graph without.
+
     python scripts/bench_sampling.py [--layers 32] [--skip-kernel] [--skip-tpot] [--json-out FILE]
     python scripts/bench_sampling.py --penalties [--layers 32] [--json-out FILE]
     python scripts/bench_sampling.py --logprobs [--layers 32] [--json-out FILE]
+    python scripts/bench_sampling.py --constraints [--layers 32] [--json-out FILE]
 """
 import argparse
 import json
@@ -36,11 +46,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llm_sharding_amd.config import LlamaConfig  # noqa: E402
+from llm_sharding_amd.ops import constraints as K  # noqa: E402
 from llm_sharding_amd.ops import logprobs as LP  # noqa: E402
 from llm_sharding_amd.ops import penalties as P  # noqa: E402
 from llm_sharding_amd.ops import sampling as S  # noqa: E402
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, StageEngine  # noqa: E402
-from llm_sharding_amd.runtime.sampling import PenaltyState, SamplingDecodeGraph, SamplingParams  # noqa: E402
+from llm_sharding_amd.runtime.sampling import (ConstraintState, PenaltyState, SamplingDecodeGraph,  # noqa: E402
+                                               SamplingParams)
 
 DEV = "cuda"
 
@@ -272,6 +284,115 @@ def bench_tpot_logprobs(layers: int, rows: int, n_top: int = 5, rounds: int = 5,
             "logprobs_spread_ms": round(max(times["logprobs"]) - min(times["logprobs"]), 4)}
 
 
+def bench_logit_process(rows: int, mode: str, V: int = 32000, reread: bool = False) -> dict:
+    """``mode``: "bias" (320 entries), "automaton", "automaton_minp". ``reread``: the min-p pass
+    re-reads the row from L2 instead of keeping it in registers."""
+    from types import SimpleNamespace
+    g = torch.Generator(device=DEV).manual_seed(rows + V)
+    lg0 = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
+    lg = lg0.clone()
+    cg = torch.Generator().manual_seed(rows)
+    nxt = torch.randint(0, rows, (rows, V), generator=cg).to(torch.int16)
+    nxt[torch.rand((rows, V), generator=cg) < 0.5] = -1
+    tok = torch.stack([torch.nonzero(nxt[r] >= 0)[0, 0] for r in range(rows)])
+    nxt[torch.arange(rows), tok] = torch.arange(rows, dtype=torch.int16)   # the fed token loops: slot r stays in state r
+    tok = tok.to(torch.int32).to(DEV)
+    auto = mode != "bias"
+    tb = SimpleNamespace(
+        arena=nxt.to(DEV),
+        astate=(torch.arange(rows, dtype=torch.int32) if auto else torch.full((rows,), -1, dtype=torch.int32)).to(DEV),
+        abase=torch.zeros(rows, dtype=torch.int32, device=DEV),
+        bias_n=torch.full((rows,), 0 if auto else K.BIAS_MAX, dtype=torch.int32, device=DEV),
+        bias_tok=torch.stack([torch.randperm(V, generator=cg)[:K.BIAS_MAX]
+                              for _ in range(rows)]).to(torch.int32).to(DEV),
+        bias_val=torch.randn((rows, K.BIAS_MAX), generator=cg).to(DEV),
+        min_until=torch.zeros(rows, dtype=torch.int32, device=DEV),
+        minp_delta=torch.full((rows,), 0.7 * -2.9957 if mode == "automaton_minp" else float("-inf"), device=DEV),
+        fault=torch.zeros(rows, dtype=torch.int32, device=DEV),
+        eos=torch.full((K.N_EOS,), -1, dtype=torch.int32, device=DEV))
+    slot = torch.arange(rows, dtype=torch.int32, device=DEV)
+    ctr = torch.full((rows,), 100, dtype=torch.int32, device=DEV)
+    a0 = tb.astate.clone()
+
+    def run():
+        K.logit_process(lg, V, rows, slot, tok, ctr, tb, reread=reread)
+
+    def restore():
+        lg.copy_(lg0)
+        tb.astate.copy_(a0)
+
+    def restore_run():
+        restore()
+        run()
+
+    for _ in range(3):
+        restore_run()
+    torch.cuda.synchronize()
+    steady = statistics.median(1e3 * _graph_events(run, 50) for _ in range(3))       # masks in place: no stores
+    both = [1e3 * _graph_events(restore_run, 50) for _ in range(5)]
+    copy = [1e3 * _graph_events(restore, 50) for _ in range(5)]
+    fresh = statistics.median(both) - statistics.median(copy)
+    read_mb = rows * V * (4 if auto else 0) / 1e6
+    return {"kernel": "lsa_logit_process", "mode": mode + ("_reread" if reread else ""), "rows": rows, "V": V, "steady_graphed_us": round(steady, 2),
+            "fresh_graphed_us": round(fresh, 2), "fresh_spread_us": round(max(both) - min(both), 2),
+            "restore_us": round(statistics.median(copy), 2), "read_MB": round(read_mb, 2),
+            "steady_GBps": round(read_mb / steady * 1e3, 1) if auto else None}
+
+
+def bench_tpot_constraints(layers: int, rows: int, rounds: int = 5, steps: int = 20) -> dict:
+    cfg = LlamaConfig(num_hidden_layers=layers, vocab_size=32000, max_position_embeddings=512, name=f"7B-{layers}L")
+    eng = StageEngine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                      max_slots=rows, max_seq=128, max_prefill_rows=max(rows, 128))
+    # 64 choices of 48 tokens: no row reaches the end of its choice inside a window of 23 steps
+    cg = torch.Generator().manual_seed(11)
+    choices = [torch.randint(3, cfg.vocab_size, (48,), generator=cg).tolist() for _ in range(64)]
+    cs = ConstraintState(eng, rows, state_rows=64 * 48 + 2)
+    graphs = {"sampling": SamplingDecodeGraph(eng, rows, "full"),
+              "choices": SamplingDecodeGraph(eng, rows, "full", constraints=cs)}
+    for r in range(rows):
+        graphs["sampling"].set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r))
+        sp = SamplingParams(0.7, top_p=0.9, seed=1000 + r, choices=choices)
+        cs.admit(r, sp, 1)
+        graphs["choices"].set_params(r, sp)
+    for g in graphs.values():
+        g.capture()
+    a0 = cs.astate.clone()
+    tok0 = torch.randint(3, cfg.vocab_size, (rows,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(DEV)
+    times = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            g.set_positions()
+            g.tokens.copy_(tok0)
+            cs.astate.copy_(a0)
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            times[name].append(_events(g.replay, steps))
+    ts, tc = statistics.median(times["sampling"]), statistics.median(times["choices"])
+    del graphs, cs, eng
+    torch.cuda.empty_cache()
+    return {"layers": layers, "rows": rows, "sampling_ms": round(ts, 4), "choices_ms": round(tc, 4),
+            "delta_ms": round(tc - ts, 4), "delta_pct": round(100 * (tc - ts) / ts, 2),
+            "sampling_spread_ms": round(max(times["sampling"]) - min(times["sampling"]), 4),
+            "choices_spread_ms": round(max(times["choices"]) - min(times["choices"]), 4)}
+
+
+def main_constraints(a) -> dict:
+    out = {"kernel": [], "tpot": []}
+    for rows in (1, 512):
+        rs = [bench_logit_process(rows, m) for m in ("bias", "automaton", "automaton_minp")]
+        rs.append(bench_logit_process(rows, "automaton_minp", reread=True))
+        for r in rs + [bench_penalize(rows), bench_kernel(rows, 32000, "top_p", graphed=True)]:
+            out["kernel"].append(r)
+            print(json.dumps(r), flush=True)
+    if not a.skip_tpot:
+        for rows in (1, 512):
+            r = bench_tpot_constraints(a.layers, rows)
+            out["tpot"].append(r)
+            print(json.dumps(r), flush=True)
+    return out
+
+
 def main_logprobs(a) -> dict:
     out = {"kernel": [], "tpot": []}
     for rows in (1, 512):
@@ -307,12 +428,15 @@ def main():
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--penalties", action="store_true", help="measure lsa_penalize and the penalised step instead")
     ap.add_argument("--logprobs", action="store_true", help="measure lsa_logprobs and the step with logprobs=5 instead")
+    ap.add_argument("--constraints", action="store_true",
+                    help="measure lsa_logit_process and the step under choices instead")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sampling.py measures on the GPU: none found")
-    special = a.penalties or a.logprobs
-    out = main_penalties(a) if a.penalties else (main_logprobs(a) if a.logprobs else {"kernel": [], "tpot": []})
+    special = a.penalties or a.logprobs or a.constraints
+    out = (main_penalties(a) if a.penalties else main_logprobs(a) if a.logprobs else
+           main_constraints(a) if a.constraints else {"kernel": [], "tpot": []})
     for V in (() if a.skip_kernel or special else (32000, 128256)):
         for rows in (1, 128, 512):
             for mode in ("temperature", "top_k", "top_p"):

@@ -24,9 +24,12 @@ finished request to stdout and, if ``reply_to`` is given, pushes ``{"request_id"
 pipeline stage only), and ``repetition_penalty``, ``presence_penalty`` and ``frequency_penalty``
 keys penalise repeated tokens on the device (also at temperature 0; one stage only); a
 ``logprobs`` key (0..20) adds a ``"logprobs"`` dict to the reply: per-token ``token_logprobs``,
-``ranks`` and that many ``top_logprobs`` alternatives (one stage only);
+``ranks`` and that many ``top_logprobs`` alternatives (one stage only); ``logit_bias``,
+``banned_token_ids``, ``min_tokens``, ``min_p``, ``allowed_token_ids`` and ``choices`` keys constrain
+the output on the device (one stage only; ``--state-rows`` sizes the automaton arena);
 ``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty
---logprobs`` do the same for the synthetic load test (request i seeded with ``--seed`` + i).
+--logprobs --min-p --min-tokens`` do the same for the synthetic load test (request i seeded with
+``--seed`` + i).
 ``--prefix-slots P`` adds a pool of P KV slots for shared prompt prefixes: a request's
 ``cache_prefix`` key declares its leading tokens worth keeping, every request forks the longest
 pooled match instead of prefilling it, and an ``n`` key asks for that many samples of one prompt
@@ -78,6 +81,12 @@ def main():
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
     ap.add_argument("--logprobs", type=int, default=None, metavar="N",
                     help="load test: collect per-token log-probabilities and N (0..20) alternatives (one stage only)")
+    ap.add_argument("--min-p", type=float, default=None,
+                    help="load test: drop tokens with p < min_p * p_max (needs --temperature; one stage only)")
+    ap.add_argument("--min-tokens", type=int, default=0, help="load test: no EOS before this many tokens (one stage only)")
+    ap.add_argument("--state-rows", type=int, default=256,
+                    help="rows of the automaton arena of constrained requests (one per automaton state; allocated "
+                         "with the first constrained request: 16 MB at V = 32000, 66 MB at V = 128256 for 256)")
     ap.add_argument("--prefix-slots", type=int, default=0, metavar="P",
                     help="KV slots of the prefix pool (0: no prefix caching, no parallel samples)")
     ap.add_argument("--shared-prefix-len", type=int, default=0, metavar="L",
@@ -131,7 +140,7 @@ def main():
     srv = PipelineServer(cfg, source, rank, world, st.start, st.end, dev, batch=rc.batch, microbatches=M,
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
-                         streams=rc.streams, prefix_slots=a.prefix_slots)
+                         streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows)
     if rank != 0:
         srv.serve()
     elif a.requests:
@@ -141,10 +150,11 @@ def main():
             ids = shared + torch.randint(3, cfg.vocab_size, (a.prompt_len - len(shared),), generator=g).tolist()
             pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
             kw = {}
-            if a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None:
+            if (a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None or a.min_p is not None
+                    or a.min_tokens):
                 from llm_sharding_amd.runtime.sampling import SamplingParams
                 kw["sampling"] = SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i * a.n, *pen,
-                                                logprobs=a.logprobs)
+                                                logprobs=a.logprobs, min_p=a.min_p, min_tokens=a.min_tokens)
             if a.n > 1:
                 srv.submit_n(ids, a.n, rc.max_new_tokens, eos_ids=(), **kw)
             elif shared and a.prefix_slots:
