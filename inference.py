@@ -81,6 +81,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--choice", action="append", default=[], metavar="TEXT",
                     help="the output is exactly one of the given texts (tokenised without special tokens), then EOS; "
                          "repeatable")
+    ap.add_argument("--regex", default=None, metavar="PATTERN",
+                    help="the output, as bytes, fully matches PATTERN (a byte-level DFA walked over the vocabulary's "
+                         "byte strings on the device), then EOS")
     ap.add_argument("--speculative", type=int, default=0, metavar="K",
                     help="speculative decoding: verify K (1..15) n-gram drafts per step (0: off)")
     ap.add_argument("--spec-ngram", default="1,3", metavar="MIN,MAX",
@@ -110,6 +113,8 @@ def speculative_from_args(a, sp):
     if constraint_flags(a):
         raise SystemExit("[ERROR] --speculative does not combine with --logit-bias, --ban, --min-tokens, --min-p or "
                          "--choice (the constraint state is sequential per token)")
+    if a.regex is not None:
+        raise SystemExit("[ERROR] --speculative does not combine with --regex (the DFA state is sequential per token)")
     return a.speculative, (nmin, nmax)
 
 
@@ -123,7 +128,7 @@ def sampling_from_args(a, choices=None):
     from llm_sharding_amd.runtime.sampling import SamplingParams
     pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
     if (a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0)
-            and a.logprobs is None and not constraint_flags(a)):
+            and a.logprobs is None and not constraint_flags(a) and a.regex is None):
         return None
     bias = {}
     for item in a.logit_bias:
@@ -134,23 +139,35 @@ def sampling_from_args(a, choices=None):
             raise SystemExit(f"[ERROR] --logit-bias takes ID:VAL, got {item!r}")
     try:
         sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen, logprobs=a.logprobs, logit_bias=bias or None,
-                            banned_token_ids=a.ban or None, min_tokens=a.min_tokens, min_p=a.min_p, choices=choices)
+                            banned_token_ids=a.ban or None, min_tokens=a.min_tokens, min_p=a.min_p, choices=choices,
+                            regex=a.regex)
     except ValueError as e:
-        if constraint_flags(a):
+        if constraint_flags(a) or a.regex is not None:
             raise SystemExit(f"[ERROR] {e}")
         raise
     return None if sp.plain else sp
 
 
+def join_regex_arg(argv):
+    """``--regex PATTERN`` as ``--regex=PATTERN``: argparse would take a pattern that starts with
+    '-' (``-?[0-9]+``) for an option."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):
+        if argv[i] == "--regex":
+            argv[i:i + 2] = ["--regex=" + argv[i + 1]]
+            break
+    return argv
+
+
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    a = build_parser().parse_args(join_regex_arg(argv))
     sp = sampling_from_args(a)
     spec = speculative_from_args(a, sp)
     if sp is not None and a.hf_compare:
         raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling and penalty flags")
-    if constraint_flags(a) and (a.score or a.hf_compare):
+    if (constraint_flags(a) or a.regex is not None) and (a.score or a.hf_compare):
         raise SystemExit("[ERROR] --score and --hf-compare do not combine with --logit-bias, --ban, --min-tokens, "
-                         "--min-p or --choice")
+                         "--min-p, --choice or --regex")
     if a.shards:
         cfg = LlamaConfig.from_pretrained(a.shards)
         src, tok = ShardFolderSource(a.shards, cfg), load_tokenizer(a.shards)
@@ -178,8 +195,11 @@ def main(argv=None):
         return out
     if sp is not None:
         lp = {}
-        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist(), lp_out=lp)
+        out, dt_s = sample_tokens(eng, h, ids.numel(), a.max_new_tokens, sp, prompt_ids=ids.tolist(), lp_out=lp,
+                                  tok=tok)
         out = report(a, cfg, tok, ids, out, dt_s)
+        if sp.grammar is not None:
+            report_regex(sp, tok, cfg, out)
         if lp:
             print_logprobs(tok, out, lp)
         return out
@@ -259,16 +279,27 @@ def speculative_tokens(eng, h, ids: list, n_new: int, k: int, ngram: tuple, sp, 
     return r["tokens"], dt_s, {"steps": len(r["accepted"]), "tokens": sum(r["accepted"]), "matched": r["matched"]}
 
 
-def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out=None) -> tuple:
+def report_regex(sp, tok, cfg, out: list) -> None:
+    """--regex: the generated bytes and whether they match (an output cut by --max-new-tokens is a
+    live prefix of a match)."""
+    from llm_sharding_amd.ops.grammar import VocabBytes
+    data = VocabBytes.from_tokenizer(tok, cfg.vocab_size).decode([t for t in out if t not in cfg.eos_ids])
+    full = sp.grammar.accepts(data)
+    print(f"[INFO] regex {sp.regex!r}: output {data!r} " + ("matches" if full else
+          ("is a prefix of a match (cut by --max-new-tokens)" if sp.grammar.walk(data) >= 0 else "DOES NOT MATCH")))
+
+
+def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out=None, tok=None) -> tuple:
     """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from ``Sampler.sample``, the rest from a captured
     ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
     sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along, with a
-    constraint its ``ConstraintState``. With
+    constraint its ``ConstraintState``, with a regex its ``GrammarState`` over the byte strings of ``tok``'s
+    vocabulary. With
     ``sp.logprobs`` the tokens' log-probabilities, ranks and alternatives go into the dict
     ``lp_out`` (``lp``, ``rank``, ``top``: per token a list of (id, logprob))."""
-    from llm_sharding_amd.runtime.sampling import (ConstraintState, EagerSamplingDecode, PenaltyState, Sampler,
-                                                   SamplingDecodeGraph)
+    from llm_sharding_amd.runtime.sampling import (ConstraintState, EagerSamplingDecode, GrammarState, PenaltyState,
+                                                   Sampler, SamplingDecodeGraph)
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
     pen, kw = None, {}
     if sp.penalized:
@@ -287,10 +318,21 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out
         print(f"[INFO] constraints: {len(sp.bias_entries())} bias entries, min_tokens {sp.min_tokens}, "
               f"min_p {sp.min_p}, {len(sp.choices or ())} choices")
         kw["constraints"] = con
+    gram = None
+    if sp.grammar is not None:
+        from llm_sharding_amd.ops.grammar import VocabBytes
+        try:
+            gram = GrammarState(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size),
+                                dfa_rows=sp.grammar.n_states)
+            gram.admit(0, sp)
+        except ValueError as e:
+            raise SystemExit(f"[ERROR] {e}")
+        print(f"[INFO] regex {sp.regex!r}: a byte-level DFA of {sp.grammar.n_states} states")
+        kw["grammar"] = gram
     want_lp = sp.logprobs is not None
-    first = Sampler(eng, pen, con).sample(h, [n_prompt - 1], [sp], [n_prompt],
-                                          slots=[0] if pen is not None or con is not None else None,
-                                          return_logprobs=want_lp)
+    stateful = pen is not None or con is not None or gram is not None
+    first = Sampler(eng, pen, con, gram).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if stateful else None,
+                                                return_logprobs=want_lp)
     steps = []
     if want_lp:
         first, lp0 = first

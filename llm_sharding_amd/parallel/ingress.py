@@ -125,7 +125,10 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     reply; optional ``logit_bias`` (token id, as a string or an integer, -> bias),
     ``banned_token_ids``, ``min_tokens``, ``min_p``, ``allowed_token_ids`` and ``choices`` (a list
     of token-id sequences): constrained decoding, refused with an error reply when a field is
-    invalid or the automaton does not fit the server's arena; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
+    invalid or the automaton does not fit the server's arena; optional ``regex``: the output's bytes
+    fully match the pattern (``ops.grammar``), refused with an error reply on a syntax error, a
+    server without ``vocab_bytes``, a DFA that does not fit its arena or a state that allows no
+    token; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
     optional ``n > 1``: that many samples of each prompt sharing one prefill, answered with a
     ``"choices"`` list - needs a server with ``prefix_slots``). Returns the number of requests
     queued."""

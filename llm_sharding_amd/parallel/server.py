@@ -95,6 +95,7 @@ class Request:
     entry: Optional["_PoolEntry"] = None  # FORKING: the pool entry it forks from ...
     fork_len: int = 0  # ... and how many tokens
     constraint: Optional[object] = None  # sampling.constrained: its CompiledConstraint (automaton acquired)
+    grammar: Optional[object] = None  # sampling.regex: its ByteDFA (rows of the DFA arena acquired)
 
     @property
     def ttft_ms(self) -> float:
@@ -160,7 +161,8 @@ class PipelineServer:
                  device="cpu", batch: int = 8, microbatches: int = 1, max_seq: int = 2048,
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
                  ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
-                 prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256):
+                 prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256,
+                 vocab_bytes=None, dfa_rows: int = 4096):
         self.cfg, self.rank, self.world = cfg, rank, world
         # prefix pool: engine slots >= B * M, never decoded, in no micro-batch and no graph
         self.P = int(prefix_slots)
@@ -211,6 +213,13 @@ class PipelineServer:
         self.state_rows = int(state_rows)
         self.constraints = None
         self._arena = None
+        # regex: the DFA arena (dfa_rows rows of 512 B), the vocabulary's byte strings and the
+        # per-slot states exist, and the graphs carry the lsa_grammar_mask launch, from the first
+        # request with a regex on; vocab_bytes (ops.grammar.VocabBytes) is what such requests need
+        self.vocab_bytes, self.dfa_rows = vocab_bytes, int(dfa_rows)
+        self.grammar = None
+        self._garena = None
+        self._gcheck = None
         self._lp_out: List = [None] * microbatches  # logprobs of a micro-batch's outstanding command
         self._build_graphs()
         # rank 0 state
@@ -249,14 +258,15 @@ class PipelineServer:
                     from ..runtime.sampling import SamplingDecodeGraph
                     g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S,
                                             penalties=self.penalties, logprobs=self.logprobs_on,
-                                            constraints=self.constraints)
+                                            constraints=self.constraints, grammar=self.grammar)
                 else:
                     g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
                 self.graphs.append(g.capture())
         for st in self.streams:  # after weight loading and graph capture on the current stream
             st.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _enable_sampling(self, penalties: bool = False, logprobs: bool = False, constraints: bool = False) -> None:
+    def _enable_sampling(self, penalties: bool = False, logprobs: bool = False, constraints: bool = False,
+                         grammar: bool = False) -> None:
         """First non-greedy request (world == 1): build the Sampler and, in graph mode, replace
         every micro-batch's greedy graph by a SamplingDecodeGraph that takes over its device
         positions and tokens. Rows start greedy; a slot's parameters are written on admission.
@@ -267,8 +277,10 @@ class PipelineServer:
             self.penalties = PenaltyState(self.eng, self.B * self.M)
         if constraints:
             self.constraints = self._new_constraints()
+        if grammar:
+            self.grammar = self._new_grammar()
         self.logprobs_on = self.logprobs_on or logprobs
-        self.sampler = Sampler(self.eng, self.penalties, self.constraints)
+        self.sampler = Sampler(self.eng, self.penalties, self.constraints, self.grammar)
         self.sampling_on = True
         self._swap_sampling_graphs()
 
@@ -287,6 +299,23 @@ class PipelineServer:
         parameters over. Until then no graph holds that kernel and no table is allocated."""
         self.constraints = self._new_constraints()
         self.sampler.constraints = self.constraints
+        self._swap_sampling_graphs()
+
+    def _new_grammar(self):
+        from ..ops.constraints import ArenaAllocator
+        from ..runtime.sampling import GrammarState
+        with self._lock:
+            if self._garena is None:
+                self._garena = ArenaAllocator(self.dfa_rows)
+        return GrammarState(self.eng, self.B * self.M, self.vocab_bytes, self.dfa_rows, allocator=self._garena)
+
+    def _enable_grammar(self) -> None:
+        """First request with a regex (sampling already on): allocate the GrammarState and, in graph
+        mode, replace every sampling graph by one whose step runs ``lsa_grammar_mask`` between
+        ``lsa_penalize`` and ``lsa_logit_process``, carrying positions, tokens and the rows'
+        parameters over. Until then no graph holds that kernel and no table is allocated."""
+        self.grammar = self._new_grammar()
+        self.sampler.grammar = self.grammar
         self._swap_sampling_graphs()
 
     def _enable_penalties(self) -> None:
@@ -316,7 +345,7 @@ class PipelineServer:
         for mb in range(self.M):
             g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S,
                                     penalties=self.penalties, logprobs=self.logprobs_on,
-                                    constraints=self.constraints)
+                                    constraints=self.constraints, grammar=self.grammar)
             g.pos.copy_(old[mb].pos)
             g.tokens.copy_(old[mb].tokens)
             for i, p in enumerate(getattr(old[mb], "params", ())):
@@ -338,7 +367,7 @@ class PipelineServer:
         sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
         if sel:
             pen = {}
-            if self.penalties is not None or self.constraints is not None:
+            if self.penalties is not None or self.constraints is not None or self.grammar is not None:
                 pen = {"slots": [slots[i] for i in sel],
                        "tokens_in": None if tokens_in is None else [tokens_in[i] for i in sel]}
             want_lp = self.logprobs_on and any(reqs[i].sampling.logprobs is not None for i in sel)
@@ -403,7 +432,12 @@ class PipelineServer:
                     if self.gpu:
                         torch.cuda.empty_cache()
                     self.constraints = self._new_constraints()
-                self.sampler = Sampler(self.eng, self.penalties, self.constraints)
+                if self.grammar is not None:  # the same for the DFA arena
+                    self.grammar = None
+                    if self.gpu:
+                        torch.cuda.empty_cache()
+                    self.grammar = self._new_grammar()
+                self.sampler = Sampler(self.eng, self.penalties, self.constraints, self.grammar)
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
@@ -554,6 +588,11 @@ class PipelineServer:
                             if r is not None and r.constraint is not None:
                                 self.constraints.admit(s, r.sampling, len(r.input_ids), compiled=r.constraint,
                                                        acquired=True)
+                    if self.grammar is not None:  # a request with a regex enters its slot
+                        for (s, _, _, _) in em:
+                            r = self.by_slot.get(s)
+                            if r is not None and r.grammar is not None:
+                                self.grammar.admit(s, r.sampling, acquired=True)
                     tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok,
                                             mb=mb)
                     if self.graph_mode:  # the slot's parameters, before its first decode step
@@ -621,7 +660,10 @@ class PipelineServer:
         ``logprobs`` of the request, and its constraint fields (``logit_bias``, ``banned_token_ids``,
         ``min_tokens``, ``min_p``, ``allowed_token_ids``, ``choices``, ``automaton``: checked here
         against the vocabulary, and the automaton's rows of the arena are reserved here - ValueError
-        when they do not fit) (None, or temperature 0 with every penalty off, no logprobs and no
+        when they do not fit), and ``regex`` (compiled when the parameters were built; here its
+        DFA is checked against the server's ``vocab_bytes`` and its rows of the DFA arena are
+        reserved - ValueError without ``vocab_bytes``, when the DFA does not fit, or when one of its
+        states allows no token of the vocabulary) (None, or temperature 0 with every penalty off, no logprobs and no
         constraint: greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
         batch it runs in. With ``logprobs`` the finished :class:`Request` holds ``token_logprobs``,
         ``ranks`` and (``logprobs >= 1``) ``top_logprobs``, one entry per generated token."""
@@ -649,6 +691,14 @@ class PipelineServer:
                     if self._arena is None:
                         self._arena = ArenaAllocator(self.state_rows)
                     self._arena.acquire(constraint.automaton)
+        grammar = None if sampling is None else sampling.grammar
+        if grammar is not None:
+            try:
+                self._reserve_grammar(grammar)
+            except ValueError:
+                if constraint is not None and constraint.automaton is not None:
+                    self._arena.release(constraint.automaton.digest)
+                raise
         with self._lock:
             rid = self._next_id
             self._next_id += 1
@@ -656,9 +706,30 @@ class PipelineServer:
         if cache_prefix is not None:
             cache_prefix = max(0, min(int(cache_prefix), len(ids) - 1))
         r = Request(rid, ids, int(max_new_tokens), eos, on_token=on_token, reply_to=reply_to, sampling=sampling,
-                    t_submit=time.perf_counter(), cache_prefix=cache_prefix, group=_group, constraint=constraint)
+                    t_submit=time.perf_counter(), cache_prefix=cache_prefix, group=_group, constraint=constraint,
+                    grammar=grammar)
         self.incoming.put(r)
         return rid
+
+    def _reserve_grammar(self, dfa) -> None:
+        """A request with a regex is submitted: check its DFA against the vocabulary's bytes and
+        reserve its rows of the DFA arena (ValueError on either)."""
+        from ..ops.constraints import ArenaAllocator
+        from ..runtime.sampling import _check_full_head, check_vocab_cache
+        if self.vocab_bytes is None:
+            raise ValueError("a regex needs the byte strings of the vocabulary: build the server with "
+                             "vocab_bytes=ops.grammar.VocabBytes.from_tokenizer(...)")
+        if self.vocab_bytes.V != self.cfg.vocab_size:
+            raise ValueError(f"vocab_bytes covers {self.vocab_bytes.V} tokens, the configuration has "
+                             f"{self.cfg.vocab_size}")
+        _check_full_head(self.eng)
+        with self._lock:
+            if self._gcheck is None:
+                self._gcheck = check_vocab_cache(self.vocab_bytes, self.cfg.eos_ids)
+            if self._garena is None:
+                self._garena = ArenaAllocator(self.dfa_rows)
+            self._gcheck(dfa)
+            self._garena.acquire(dfa)
 
     def submit_n(self, input_ids, n: int, max_new_tokens: int = 64, eos_ids=None, on_token=None,
                  reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> List[int]:
@@ -810,6 +881,12 @@ class PipelineServer:
             r.state, r.t_done = DONE, now
             if r.constraint is not None and self.constraints is not None:
                 self.constraints.release(r.slot)
+            if r.grammar is not None and self.grammar is not None:
+                fault = int(self.grammar.gfault[r.slot])
+                if fault:
+                    print(f"[WARN] request {r.rid}: grammar fault {fault} under regex {r.sampling.regex!r} (1: a token "
+                          "outside the pattern was fed, 2: a state allowed no token)", flush=True)
+                self.grammar.release(r.slot)
             mb = r.slot // self.B
             del self.by_slot[r.slot]
             self.cur_tok.pop(r.slot, None)
@@ -884,7 +961,9 @@ class PipelineServer:
             r = self.waiting.pop(0)
             if r.sampling is not None and not self.sampling_on:
                 self._enable_sampling(penalties=r.sampling.penalized, logprobs=r.sampling.logprobs is not None,
-                                      constraints=r.constraint is not None)
+                                      constraints=r.constraint is not None, grammar=r.grammar is not None)
+            if r.grammar is not None and self.grammar is None:
+                self._enable_grammar()
             if r.constraint is not None and self.constraints is None:
                 self._enable_constraints()
             if r.sampling is not None and r.sampling.penalized and self.penalties is None:

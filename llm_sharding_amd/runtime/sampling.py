@@ -18,6 +18,11 @@ path that exists only when a request asks for it.
   (``ops.constraints``: logit bias, banned tokens, ``min_tokens``, min-p, token automata); it
   exists only once a request asks for one of them, and a graph or Sampler built without it runs
   exactly the code above. The order is penalise -> process -> sample -> logprobs.
+* :class:`GrammarState` - the byte-level DFA arena, the vocabulary's byte strings and the per-slot
+  states of regex-constrained decoding (``ops.grammar``, ``SamplingParams.regex``); it exists only
+  once a request carries a regex, and a graph or Sampler built without it runs exactly the code
+  above. With it the order is penalise -> grammar mask -> process -> sample -> logprobs: min-p sees
+  the masked row.
 * Log-probabilities (``SamplingParams.logprobs``, ``ops.logprobs``): :meth:`Sampler.logprobs`,
   ``SamplingDecodeGraph(..., logprobs=True)`` (one ``lsa_logprobs`` launch behind
   ``argmax_finalize``; a graph built without it captures exactly the step above) and
@@ -39,6 +44,7 @@ import numpy as np
 import torch
 
 from ..ops import constraints as K
+from ..ops import grammar as G
 from ..ops import logprobs as LP
 from ..ops import penalties as P
 from ..ops import sampling as S
@@ -66,7 +72,13 @@ class SamplingParams:
     sequences, then EOS) and ``automaton`` (an explicit :class:`ops.constraints.TokenAutomaton`,
     the hook of an external regex / grammar compiler) exclude one another, and ``banned_token_ids``,
     a ``-inf`` bias and ``min_tokens``: the automaton decides what may appear and when the output
-    ends, so a row can never lose every column."""
+    ends, so a row can never lose every column.
+
+    ``regex`` (``ops.grammar``): the output, as bytes, fully matches this pattern - compiled here
+    into a byte-level DFA (:attr:`grammar`), so a syntax error surfaces at construction. It excludes
+    ``allowed_token_ids``, ``choices``, ``automaton``, ``banned_token_ids``, a ``-inf`` bias and
+    ``min_tokens`` for the same reason; a finite ``logit_bias``, ``min_p``, the penalties, top-k /
+    top-p and ``logprobs`` combine with it."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
@@ -82,9 +94,24 @@ class SamplingParams:
     allowed_token_ids: Optional[list] = None
     choices: Optional[list] = None
     automaton: Optional[Any] = None
+    regex: Optional[str] = None
 
     def __post_init__(self):
         self._check_constraints()
+        self._grammar = None
+        if self.regex is not None:
+            if not isinstance(self.regex, str):
+                raise ValueError(f"regex must be a str, got {self.regex!r}")
+            clash = [k for k in ("allowed_token_ids", "choices", "automaton", "banned_token_ids")
+                     if getattr(self, k) is not None]
+            if self.min_tokens:
+                clash.append("min_tokens")
+            if any(b == float("-inf") for _, b in self.bias_entries()) and "banned_token_ids" not in clash:
+                clash.append("a -inf bias")
+            if clash:
+                raise ValueError(f"regex cannot be combined with {' / '.join(clash)}: the pattern decides what may "
+                                 "appear and when the output ends")
+            self._grammar = _compile_regex(self.regex)
         self.temperature, self.top_k, self.top_p = float(self.temperature), int(self.top_k), float(self.top_p)
         if not self.temperature >= 0.0 or self.temperature == float("inf"):
             raise ValueError(f"temperature must be a finite value >= 0, got {self.temperature}")
@@ -192,10 +219,17 @@ class SamplingParams:
                     or self.allowed_token_ids is not None or self.choices is not None or self.automaton is not None)
 
     @property
+    def grammar(self):
+        """The compiled :class:`ops.grammar.ByteDFA` of ``regex`` (None without one): the request
+        needs a :class:`GrammarState`."""
+        return self._grammar
+
+    @property
     def plain(self) -> bool:
         """Needs no sampling path at all: temperature 0, every penalty off, no logprobs, no
-        constraint."""
-        return self.greedy and not self.penalized and self.logprobs is None and not self.constrained
+        constraint, no regex."""
+        return (self.greedy and not self.penalized and self.logprobs is None and not self.constrained
+                and self._grammar is None)
 
     @property
     def n_top(self) -> int:
@@ -206,13 +240,29 @@ class SamplingParams:
     def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
         """``temperature / top_k / top_p / seed / repetition_penalty / presence_penalty /
         frequency_penalty / logprobs / logit_bias / banned_token_ids / min_tokens / min_p /
-        allowed_token_ids / choices`` keys of a request dict (``logit_bias`` with string or integer
+        allowed_token_ids / choices / regex`` keys of a request dict (``logit_bias`` with string or integer
         keys); None (greedy) when none of them is present."""
         keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty",
-                "logprobs", "logit_bias", "banned_token_ids", "min_tokens", "min_p", "allowed_token_ids", "choices")
+                "logprobs", "logit_bias", "banned_token_ids", "min_tokens", "min_p", "allowed_token_ids", "choices",
+                "regex")
         if not any(d.get(k) is not None for k in keys):
             return None
         return cls(**{k: d[k] for k in keys if d.get(k) is not None})
+
+
+_REGEX_CACHE: dict = {}
+
+
+def _compile_regex(pattern: str):
+    """``ByteDFA.from_regex`` behind a small cache: a ByteDFA is immutable, and servers see the same
+    patterns again and again."""
+    dfa = _REGEX_CACHE.get(pattern)
+    if dfa is None:
+        dfa = G.ByteDFA.from_regex(pattern)
+        if len(_REGEX_CACHE) >= 256:
+            _REGEX_CACHE.pop(next(iter(_REGEX_CACHE)))
+        _REGEX_CACHE[pattern] = dfa
+    return dfa
 
 
 GREEDY = SamplingParams(0.0, 0, 1.0, 0)
@@ -417,17 +467,153 @@ class ConstraintState:
         return logits
 
 
+class GrammarState:
+    """The tables of regex-constrained decoding (``ops.grammar``) on the engine's device: the DFA
+    arena ``int16 [dfa_rows, 256]`` with its ``accept`` bytes (513 B per state whatever the
+    vocabulary - 2 MB at the default 4096 rows, where the dense arena of :class:`ConstraintState`
+    takes 64 KB per state at a vocabulary of 32000), the vocabulary's byte strings (``offsets``,
+    ``data``), the per-slot rows ``gstate / gbase / gfault`` (12 B per slot) and the configuration's
+    EOS ids. Built when the first request with a regex arrives. ``allocator`` (an
+    :class:`ops.constraints.ArenaAllocator` of ``dfa_rows`` rows, by default a new one) places DFAs
+    in contiguous row ranges and shares them by content digest; a DFA's rows are uploaded when its
+    first request is admitted."""
+
+    def __init__(self, eng: StageEngine, n_slots: int, vocab: "G.VocabBytes", dfa_rows: int = 4096,
+                 allocator: Optional[K.ArenaAllocator] = None):
+        _check_full_head(eng)
+        self.eng, self.n_slots, self.dfa_rows, self.vocab = eng, int(n_slots), int(dfa_rows), vocab
+        if not isinstance(vocab, G.VocabBytes) or vocab.V != eng.cfg.vocab_size:
+            raise ValueError(f"GrammarState: a VocabBytes over the configuration's {eng.cfg.vocab_size} tokens, got "
+                             f"{getattr(vocab, 'V', None)}")
+        self.alloc = K.ArenaAllocator(self.dfa_rows) if allocator is None else allocator
+        if self.alloc.state_rows != self.dfa_rows or self.n_slots < 1:
+            raise ValueError("GrammarState: the allocator must cover dfa_rows rows, and n_slots >= 1")
+        dev, n = eng.device, self.n_slots
+        self.arena = torch.full((self.dfa_rows, 256), -1, dtype=torch.int16, device=dev)
+        self.accept = torch.zeros(self.dfa_rows, dtype=torch.uint8, device=dev)
+        self.offsets = torch.from_numpy(np.array(vocab.offsets)).to(dev)
+        self.data = torch.from_numpy(np.array(vocab.data)).to(dev)
+        self.gstate = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.gbase = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.gfault = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.eos_ids = [int(e) for e in eng.cfg.eos_ids][:K.N_EOS]
+        self.eos = torch.tensor(self.eos_ids + [-1] * (K.N_EOS - len(self.eos_ids)), dtype=torch.int32, device=dev)
+        self.resident: set = set()      # digests whose rows are in the arena
+        self.held: dict = {}            # slot -> digest of the DFA it holds
+        self.checked = check_vocab_cache(vocab, self.eos_ids)
+
+    def check(self, dfa: "G.ByteDFA") -> None:
+        """ValueError unless every state of ``dfa`` allows at least one token of this vocabulary."""
+        self.checked(dfa)
+
+    def admit(self, slot: int, params: Optional[SamplingParams], acquired: bool = False) -> None:
+        """A request enters ``slot``: point ``gstate`` at its DFA's start state (uploading the DFA's
+        rows when it is new). ``acquired``: the caller already holds the allocator's reference and
+        has run :meth:`check` (the server does both when the request is submitted)."""
+        if not 0 <= slot < self.n_slots:
+            raise ValueError(f"slot {slot} outside the grammar tables of {self.n_slots}")
+        self.release(slot)
+        dfa = None if params is None else params.grammar
+        if dfa is None:
+            return
+        if not acquired:
+            self.check(dfa)
+        d = dfa.digest
+        base = self.alloc.base(d) if acquired else self.alloc.acquire(dfa)
+        self.held[slot] = d
+        if d not in self.resident:
+            S = dfa.n_states
+            flags = dfa.accept.astype(np.uint8) * G.ACCEPT
+            flags[S - 1] |= G.LAST
+            self.arena[base:base + S] = torch.from_numpy(np.array(dfa.next)).to(self.arena.device)
+            self.accept[base:base + S] = torch.from_numpy(flags).to(self.arena.device)
+            if self.eng.gpu:  # streams other than this one may admit the same DFA next
+                torch.cuda.current_stream(self.arena.device).synchronize()
+            self.resident.add(d)
+        self.gbase[slot] = base
+        self.gstate[slot] = base
+        self.gfault[slot] = 0
+
+    def release(self, slot: int) -> None:
+        """Clear ``slot``; the DFA it held loses one reference (``gfault`` stays readable until the
+        next :meth:`admit`)."""
+        d = self.held.pop(slot, None)
+        if d is not None and self.alloc.release(d):
+            self.resident.discard(d)
+        self.gstate[slot] = -1
+
+    def apply(self, logits: torch.Tensor, slots, tokens_in) -> torch.Tensor:
+        """Advance ``slots[i]`` by the bytes of ``tokens_in[i]`` (None: nothing) and mask row i of
+        bf16 ``logits`` [n, >= vocab_size]: ``lsa_grammar_mask`` in place on the GPU, the numpy
+        reference on a CPU engine. Returns the masked logits."""
+        n, V = logits.shape[0], self.eng.cfg.vocab_size
+        slots = [int(s) for s in slots]
+        if len(slots) != n or (tokens_in is not None and len(tokens_in) != n):
+            raise ValueError(f"grammar: {n} rows, {len(slots)} slots")
+        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
+            raise ValueError(f"grammar: slots {slots} must be distinct and below {self.n_slots}")
+        if not self.eng.gpu:
+            out, gst, flt = G.grammar_mask_reference(logits.to(torch.bfloat16), V, self, slots, tokens_in)
+            self.gstate.copy_(torch.from_numpy(gst))
+            self.gfault.copy_(torch.from_numpy(flt))
+            return out
+        dev = self.eng.device
+        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
+        G.grammar_mask(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin, self)
+        return logits
+
+
+def check_vocab_cache(vocab: "G.VocabBytes", eos_ids):
+    """A function ``check(dfa)`` that raises ValueError unless every state of ``dfa`` allows at least
+    one token of ``vocab`` - so a row can never lose every column. First the cheap sufficient test
+    (the state accepts and an EOS id exists, or a live byte of it exists as a one-byte token), then,
+    only for the states that fail it, the exact vectorised walk. Results are kept per digest."""
+    eos = [int(e) for e in eos_ids if 0 <= int(e) < vocab.V]
+    ln = np.diff(vocab.offsets)
+    one = ln == 1
+    one[eos] = False                      # an EOS id's own bytes are ignored
+    single = np.zeros(256, dtype=bool)
+    single[vocab.data[vocab.offsets[:-1][one]]] = True
+    done: dict = {}
+
+    def check(dfa) -> None:
+        bad = done.get(dfa.digest)
+        if bad is None:
+            ok = ((np.asarray(dfa.next) >= 0) & single[None, :]).any(axis=1)
+            if eos:
+                ok |= np.asarray(dfa.accept)
+            bad = -1
+            rest = np.nonzero(~ok)[0]
+            for c0 in range(0, rest.size, 64):  # the exact walk, 64 states at a time
+                alive = dfa.step_tokens(vocab, rest[c0:c0 + 64]) >= 0
+                alive[:, eos] = False
+                stuck = np.nonzero(~alive.any(axis=1))[0]
+                if stuck.size:
+                    bad = int(rest[c0 + stuck[0]])
+                    break
+            if len(done) >= 1024:
+                done.pop(next(iter(done)))
+            done[dfa.digest] = bad
+        if bad >= 0:
+            raise ValueError(f"regex {dfa.pattern!r}: state {bad} of its automaton allows no token of this "
+                             "vocabulary (no token's bytes continue a match there)")
+
+    return check
+
+
 class Sampler:
     """Logits and sampled tokens of a stage that holds the whole lm_head. ``penalties``: the
     stage's :class:`PenaltyState`, applied by :meth:`sample` to the rows given ``slots``;
-    ``constraints``: its :class:`ConstraintState`, applied behind the penalties."""
+    ``grammar``: its :class:`GrammarState`, applied behind the penalties; ``constraints``: its
+    :class:`ConstraintState`, applied behind both."""
 
     def __init__(self, eng: StageEngine, penalties: Optional[PenaltyState] = None,
-                 constraints: Optional[ConstraintState] = None):
+                 constraints: Optional[ConstraintState] = None, grammar: Optional[GrammarState] = None):
         _check_full_head(eng)
         self.eng = eng
         self.penalties = penalties
         self.constraints = constraints
+        self.grammar = grammar
 
     # ------------------------------------------------------------------ logits
     def logits(self, h: torch.Tensor, rows_idx=None) -> torch.Tensor:
@@ -552,7 +738,8 @@ class Sampler:
         generated) - None for the first token after a prefill, which only sees the prompt. With a
         :class:`ConstraintState` the rows of constrained requests are then processed
         (``ops.constraints``: the automaton advances by ``tokens_in[i]``), in the order penalise ->
-        process -> sample -> logprobs.
+        process -> sample -> logprobs. With a :class:`GrammarState` the rows whose slots hold a regex
+        are masked between the two (``ops.grammar``).
         ``return_logprobs``: returns ``(tokens, Logprobs)`` - the log-probabilities of the sampled
         tokens under the (penalised) logits, for the rows whose parameters ask for them."""
         logits = self.logits(h, rows_idx)
@@ -560,6 +747,10 @@ class Sampler:
             if self.penalties is None or slots is None:
                 raise RuntimeError("a penalised request needs a PenaltyState (Sampler(eng, penalties=...)) and slots=")
             logits = self.penalties.apply(logits, slots, tokens_in, params_list)
+        if any(p.grammar is not None for p in params_list):
+            if self.grammar is None or slots is None:
+                raise RuntimeError("a request with a regex needs a GrammarState (Sampler(eng, grammar=...)) and slots=")
+            logits = self.grammar.apply(logits, slots, tokens_in)
         if any(p.constrained for p in params_list):
             if self.constraints is None or slots is None:
                 raise RuntimeError("a constrained request needs a ConstraintState (Sampler(eng, constraints=...)) and "
@@ -608,14 +799,21 @@ class SamplingDecodeGraph(DecodeGraph):
     whose slots hold no constraint are skipped. The log-probabilities then describe the processed
     row. Without it the captured step is exactly the one above.
 
+    With ``grammar`` (a :class:`GrammarState` that covers this graph's slots) one
+    ``lsa_grammar_mask`` launch sits between ``lsa_penalize`` and ``lsa_logit_process``: it advances
+    the rows' DFA states by the bytes of the step's input tokens and masks every token whose bytes
+    die in the automaton; rows whose slots hold no regex are skipped. Without it the captured step
+    is exactly the one above.
+
     The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
                  history_len: int = 0, scratch: int = 0, penalties: Optional[PenaltyState] = None,
-                 debug_raw: bool = False, logprobs: bool = False, constraints: Optional[ConstraintState] = None):
+                 debug_raw: bool = False, logprobs: bool = False, constraints: Optional[ConstraintState] = None,
+                 grammar: Optional[GrammarState] = None):
         if mode not in ("full", "last"):
             raise ValueError("SamplingDecodeGraph runs the head: mode 'full' or 'last'")
-        self.sampler = Sampler(eng, penalties, constraints)
+        self.sampler = Sampler(eng, penalties, constraints, grammar)
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len, scratch=scratch)
         dev = eng.device
         self.params = [GREEDY] * rows
@@ -634,6 +832,10 @@ class SamplingDecodeGraph(DecodeGraph):
         if constraints is not None:
             if constraints.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= constraints.n_slots:
                 raise ValueError("constraints: a ConstraintState of this engine with a distinct row per graph slot")
+        self.grammar = grammar
+        if grammar is not None:
+            if grammar.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= grammar.n_slots:
+                raise ValueError("grammar: a GrammarState of this engine with a distinct row per graph slot")
         self.lp = self.n_top = self.lp_history = None
         if logprobs:
             self.n_top = torch.full((rows,), -1, dtype=torch.int32, device=dev)
@@ -650,6 +852,8 @@ class SamplingDecodeGraph(DecodeGraph):
             raise RuntimeError("a request with logprobs needs SamplingDecodeGraph(..., logprobs=True)")
         if p.constrained and self.constraints is None:
             raise RuntimeError("a constrained request needs SamplingDecodeGraph(..., constraints=ConstraintState)")
+        if p.grammar is not None and self.grammar is None:
+            raise RuntimeError("a request with a regex needs SamplingDecodeGraph(..., grammar=GrammarState)")
         self.params[row] = p
         self.temperature[row] = p.temperature
         self.top_k[row] = p.top_k
@@ -663,11 +867,12 @@ class SamplingDecodeGraph(DecodeGraph):
             self.n_top[row] = p.n_top
 
     def capture(self, warmup: bool = True) -> "SamplingDecodeGraph":
-        """The warm-up run counts tokens into the penalty state and advances the automaton states:
-        the graph's rows are restored."""
-        cs = self.constraints
+        """The warm-up run counts tokens into the penalty state and advances the automaton and
+        grammar states: the graph's rows are restored."""
+        cs, gs = self.constraints, self.grammar
         idx = self.slot.long()
         kept = None if cs is None else (cs.astate.index_select(0, idx), cs.fault.index_select(0, idx))
+        gkept = None if gs is None else (gs.gstate.index_select(0, idx), gs.gfault.index_select(0, idx))
         if self.penalties is None:
             super().capture(warmup)
         else:
@@ -677,6 +882,9 @@ class SamplingDecodeGraph(DecodeGraph):
         if kept is not None:
             cs.astate.index_copy_(0, idx, kept[0])
             cs.fault.index_copy_(0, idx, kept[1])
+        if gkept is not None:
+            gs.gstate.index_copy_(0, idx, gkept[0])
+            gs.gfault.index_copy_(0, idx, gkept[1])
         if self.lp_history is not None:
             self.lp_history.fill_(float("nan"))
         return self
@@ -695,6 +903,8 @@ class SamplingDecodeGraph(DecodeGraph):
         if self.penalties is not None:
             P.penalize(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.penalties.state,
                        self.rep, self.pres, self.freq)
+        if self.grammar is not None:
+            G.grammar_mask(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.grammar)
         if self.constraints is not None:
             K.logit_process(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.pos, self.constraints,
                             ctr_add=1)
@@ -712,13 +922,14 @@ class EagerSamplingDecode(EagerDecode):
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None, history_len: int = 0,
                  penalties: Optional[PenaltyState] = None, logprobs: bool = False,
-                 constraints: Optional[ConstraintState] = None):
+                 constraints: Optional[ConstraintState] = None, grammar: Optional[GrammarState] = None):
         if mode not in ("full", "last"):
             raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
-        self.sampler = Sampler(eng, penalties, constraints)
+        self.sampler = Sampler(eng, penalties, constraints, grammar)
         self.penalties = penalties
         self.constraints = constraints
+        self.grammar = grammar
         self.params = [GREEDY] * rows
         self.lp = self.lp_history = None
         if logprobs:
@@ -732,6 +943,8 @@ class EagerSamplingDecode(EagerDecode):
             raise RuntimeError("a request with logprobs needs EagerSamplingDecode(..., logprobs=True)")
         if p.constrained and self.constraints is None:
             raise RuntimeError("a constrained request needs EagerSamplingDecode(..., constraints=ConstraintState)")
+        if p.grammar is not None and self.grammar is None:
+            raise RuntimeError("a request with a regex needs EagerSamplingDecode(..., grammar=GrammarState)")
         self.params[row] = p
 
     def _body(self) -> None:
@@ -741,7 +954,7 @@ class EagerSamplingDecode(EagerDecode):
         h = eng.forward(h, slot, pos)
         eng.advance(self.slots, [1] * self.rows)
         pen = {}
-        if self.penalties is not None or self.constraints is not None:
+        if self.penalties is not None or self.constraints is not None or self.grammar is not None:
             pen = {"slots": self.slots, "tokens_in": self.tokens.tolist()}
         tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], return_logprobs=self.lp is not None,
                                   **pen)
@@ -797,6 +1010,6 @@ def score_prompt(eng: StageEngine, ids, top: int = 0, slot: int = 0):
     return LP.Logprobs(*(torch.cat([p[i] for p in parts]) for i in range(5)))
 
 
-__all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "ConstraintState", "CompiledConstraint",
+__all__ = ["SamplingParams", "GREEDY", "Sampler", "PenaltyState", "ConstraintState", "GrammarState", "CompiledConstraint",
            "compile_constraints", "SamplingDecodeGraph", "EagerSamplingDecode",
            "device_params", "score_prompt", "SCORE_CHUNK_BYTES"]

@@ -112,6 +112,9 @@ class _SpecState:
             raise ValueError("speculative: constrained decoding (logit_bias, banned_token_ids, min_tokens, min_p, "
                              "allowed_token_ids, choices, automaton) keeps sequential state per slot and is not "
                              "supported together with speculation")
+        if p.grammar is not None:
+            raise ValueError("speculative: a regex keeps sequential state per slot (the DFA state after every token) "
+                             "and is not supported together with speculation")
         if not p.greedy and not self.sampling:
             raise ValueError("speculative: a sampled sequence needs sampling=True")
         row = np.zeros(self.ld, dtype=np.int32)

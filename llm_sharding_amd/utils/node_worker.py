@@ -497,6 +497,12 @@ class NodeController:
                 self.tokenizer = load_tokenizer(self.shards_path)
             except Exception as e:  # noqa: BLE001 - token-id requests still work
                 _log(f"[WARNING] no tokenizer ({e}); only input_ids requests are served")
+            if self.tokenizer is not None and n == 1:  # what a request with a regex needs (one stage only)
+                from ..ops.grammar import VocabBytes
+                try:
+                    self.server.vocab_bytes = VocabBytes.from_tokenizer(self.tokenizer, mcfg.vocab_size)
+                except Exception as e:  # noqa: BLE001 - such requests are then refused one by one
+                    _log(f"[WARNING] no byte strings of the vocabulary ({e}); regex requests are refused")
         if self.verbose:
             _log(f"[INFO] pipeline stage {r}/{n}: layers [{cfg['shards_start']}, {cfg['shards_end']}) on {self.device}")
 

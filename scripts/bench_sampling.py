@@ -31,7 +31,18 @@
    ``lsa_penalize`` and ``lsa_sample`` from the same process; and the TPOT of a 7B-shaped
    ``SamplingDecodeGraph`` whose rows decode under ``choices`` against the same graph without.
 
+6. ``--grammar`` (results: profiles/grammar_mask.md, written by the run) instead: ``lsa_grammar_mask``
+   alone at 1 and 512 rows of V = 32000 over a deterministic synthetic vocabulary (256 one-byte
+   tokens plus ASCII strings of 2 to 12 bytes), 50 launches captured in one graph, steady (masks in
+   place) and fresh (logits restored in front of every launch, the copy subtracted), for a tight
+   pattern (``-?[0-9]{1,6}``), a permissive one (``[ -~]*``: every token walks to its end) and a
+   permissive DFA on each side of ``LDS_STATES`` (``[ -~]{0,N}``); ``lsa_logit_process`` with the
+   equivalent dense automaton in the same process; and the TPOT of a 7B-shaped
+   ``SamplingDecodeGraph`` without ``grammar=``, with it and no regex row, and with every row
+   under the permissive and the tight pattern.
+
     python scripts/bench_sampling.py [--layers 32] [--skip-kernel] [--skip-tpot] [--json-out FILE]
+    python scripts/bench_sampling.py --grammar [--layers 32] [--json-out FILE] [--md-out profiles/grammar_mask.md]
     python scripts/bench_sampling.py --penalties [--layers 32] [--json-out FILE]
     python scripts/bench_sampling.py --logprobs [--layers 32] [--json-out FILE]
     python scripts/bench_sampling.py --constraints [--layers 32] [--json-out FILE]
@@ -47,12 +58,13 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llm_sharding_amd.config import LlamaConfig  # noqa: E402
 from llm_sharding_amd.ops import constraints as K  # noqa: E402
+from llm_sharding_amd.ops import grammar as G  # noqa: E402
 from llm_sharding_amd.ops import logprobs as LP  # noqa: E402
 from llm_sharding_amd.ops import penalties as P  # noqa: E402
 from llm_sharding_amd.ops import sampling as S  # noqa: E402
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, StageEngine  # noqa: E402
-from llm_sharding_amd.runtime.sampling import (ConstraintState, PenaltyState, SamplingDecodeGraph,  # noqa: E402
-                                               SamplingParams)
+from llm_sharding_amd.runtime.sampling import (ConstraintState, GrammarState, PenaltyState,  # noqa: E402
+                                               SamplingDecodeGraph, SamplingParams)
 
 DEV = "cuda"
 
@@ -377,6 +389,192 @@ def bench_tpot_constraints(layers: int, rows: int, rounds: int = 5, steps: int =
             "choices_spread_ms": round(max(times["choices"]) - min(times["choices"]), 4)}
 
 
+def synthetic_vocab(V: int = 32000) -> "G.VocabBytes":
+    """0..2 special, 256 one-byte tokens, then ASCII strings of 2 to 12 bytes: letters, digits,
+    spaces and some punctuation, seeded."""
+    import numpy as np
+    rng = np.random.default_rng(32000)
+    alpha = np.frombuffer(b"etaoinshrdlucmfwypvbgkqjxz" * 3 + b"ETAOINSHRD0123456789012345  ..,-_:;()\"'/", dtype=np.uint8)
+    pieces = [b""] * 3 + [bytes([b]) for b in range(256)]
+    pieces += [rng.choice(alpha, int(rng.integers(2, 13))).tobytes() for _ in range(V - len(pieces))]
+    return G.VocabBytes.from_pieces(pieces)
+
+
+def _steady_fresh(run, restore) -> dict:
+    def restore_run():
+        restore()
+        run()
+
+    for _ in range(3):
+        restore_run()
+    torch.cuda.synchronize()
+    steady = statistics.median(1e3 * _graph_events(run, 50) for _ in range(3))       # masks in place: no stores
+    both = [1e3 * _graph_events(restore_run, 50) for _ in range(5)]
+    copy = [1e3 * _graph_events(restore, 50) for _ in range(5)]
+    return {"steady_graphed_us": round(steady, 2), "fresh_graphed_us": round(statistics.median(both) - statistics.median(copy), 2),
+            "fresh_spread_us": round(max(both) - min(both), 2), "restore_us": round(statistics.median(copy), 2)}
+
+
+def bench_grammar_mask(rows: int, pattern: str, vocab, dense: bool = True) -> list:
+    """``lsa_grammar_mask`` and ``lsa_grammar_mask_alt`` (the other LDS threshold) with every row in
+    the start state of ``pattern``'s DFA, and (``dense``) ``lsa_logit_process`` with the equivalent
+    dense automaton, on the same logits."""
+    from types import SimpleNamespace
+    V = vocab.V
+    g = torch.Generator(device=DEV).manual_seed(rows + V)
+    lg0 = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
+    lg = lg0.clone()
+    dfa = G.ByteDFA.from_regex(pattern)
+    S = dfa.n_states
+    flags = dfa.accept.astype("uint8") * G.ACCEPT
+    flags[S - 1] |= G.LAST
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=DEV)  # noqa: E731
+    tb = SimpleNamespace(arena=torch.from_numpy(dfa.next.copy()).to(DEV), accept=torch.from_numpy(flags).to(DEV),
+                         offsets=torch.from_numpy(vocab.offsets.copy()).to(DEV), data=torch.from_numpy(vocab.data.copy()).to(DEV),
+                         gstate=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                         gbase=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                         gfault=torch.zeros(rows, dtype=torch.int32, device=DEV), eos=i32([2] + [-1] * 7))
+    slot = torch.arange(rows, dtype=torch.int32, device=DEV)
+
+    def run():
+        G.grammar_mask(lg, V, rows, slot, None, tb)
+
+    def run_alt():
+        G.grammar_mask(lg, V, rows, slot, None, tb, alt=True)
+
+    def restore():
+        lg.copy_(lg0)
+
+    allowed = int((dfa.step_tokens(vocab, [0])[0] >= 0).sum())
+    out = []
+    for name, fn, alt in (("lsa_grammar_mask", run, False), ("lsa_grammar_mask_alt", run_alt, True)):
+        path = f"lds<={G.lds_states(alt)}" if S <= G.lds_states(alt) else f"global>{G.lds_states(alt)}"
+        out.append({"kernel": name, "pattern": pattern, "states": S, "path": path, "rows": rows, "V": V,
+                    "allowed": allowed, **_steady_fresh(fn, restore), "table_KB": round(S * 512 / 1024, 1)})
+    assert int(tb.gfault.sum()) == 0
+    if dense:
+        auto = dfa.to_token_automaton(vocab, [2])
+        ct = SimpleNamespace(arena=torch.from_numpy(auto.next.copy()).to(DEV),
+                             astate=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                             abase=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                             bias_n=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                             bias_tok=torch.zeros((rows, K.BIAS_MAX), dtype=torch.int32, device=DEV),
+                             bias_val=torch.zeros((rows, K.BIAS_MAX), dtype=torch.float32, device=DEV),
+                             min_until=torch.zeros(rows, dtype=torch.int32, device=DEV),
+                             minp_delta=torch.full((rows,), float("-inf"), device=DEV),
+                             fault=torch.zeros(rows, dtype=torch.int32, device=DEV), eos=i32([2] + [-1] * 7))
+        ctr = torch.full((rows,), 100, dtype=torch.int32, device=DEV)
+
+        def run_dense():
+            K.logit_process(lg, V, rows, slot, None, ctr, ct)
+
+        restore()                                 # the two kernels must produce the same row
+        run()
+        masked = lg.clone()
+        restore()
+        run_dense()
+        torch.cuda.synchronize()
+        assert torch.equal(masked.view(torch.int16), lg.view(torch.int16)), "dense and byte-level masks differ"
+        out.append({"kernel": "lsa_logit_process", "pattern": pattern, "states": auto.n_states, "path": "dense", "rows": rows,
+                    "V": V, "allowed": allowed, **_steady_fresh(run_dense, restore),
+                    "table_KB": round(auto.n_states * V * 2 / 1024, 1)})
+    return out
+
+
+def bench_tpot_grammar(layers: int, rows: int, vocab, rounds: int = 5, steps: int = 20) -> dict:
+    cfg = LlamaConfig(num_hidden_layers=layers, vocab_size=32000, max_position_embeddings=512, name=f"7B-{layers}L")
+    eng = StageEngine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                      max_slots=rows, max_seq=128, max_prefill_rows=max(rows, 128))
+    gs = GrammarState(eng, rows, vocab, dfa_rows=64)
+    graphs = {"sampling": SamplingDecodeGraph(eng, rows, "full"),
+              "grammar_idle": SamplingDecodeGraph(eng, rows, "full", grammar=gs),
+              "permissive": SamplingDecodeGraph(eng, rows, "full", grammar=gs),
+              "tight": SamplingDecodeGraph(eng, rows, "full", grammar=gs)}
+    pats = {"permissive": "[ -~]*", "tight": "-?[0-9]{1,6}"}
+    sps = {k: SamplingParams(0.7, top_p=0.9, seed=1000, regex=v) for k, v in pats.items()}
+    for r in range(rows):
+        for name, g in graphs.items():
+            kw = {"regex": pats[name]} if name in pats else {}
+            g.set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r, **kw))
+    for g in graphs.values():
+        g.capture()
+    tok0 = torch.randint(3, cfg.vocab_size, (rows,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(DEV)
+    times = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            for r in range(rows):                 # every row at the start state of the graph's pattern, or none
+                gs.admit(r, sps.get(name))
+            g.set_positions()
+            # under a pattern the first input is the one-byte token "1", which both patterns take
+            g.tokens.copy_(tok0 if name not in pats else torch.full_like(tok0, 3 + ord("1")))
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            times[name].append(_events(g.replay, steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    fault = int(gs.gfault.sum())
+    del graphs, gs, eng
+    torch.cuda.empty_cache()
+    out = {"layers": layers, "rows": rows, "gfault": fault}
+    for k, v in med.items():
+        out[f"{k}_ms"] = round(v, 4)
+        out[f"{k}_spread_ms"] = round(max(times[k]) - min(times[k]), 4)
+        if k != "sampling":
+            out[f"{k}_delta_ms"] = round(v - med["sampling"], 4)
+    return out
+
+
+def grammar_markdown(out: dict) -> str:
+    L, T = G.lds_states(), G.block_threads()
+    lines = ["# lsa_grammar_mask on MI355X", "",
+             f"`python scripts/bench_sampling.py --grammar`: `LDS_STATES` = {L} (`lsa_grammar_mask_alt`, the same kernel: "
+             f"{G.lds_states(alt=True)}), {T} threads per row (one workgroup). "
+             "V = 32000 over the synthetic vocabulary (256 one-byte tokens plus seeded ASCII strings of 2 to 12 bytes); "
+             "50 launches captured in one graph, every row in its pattern's start state. steady: the masks are already "
+             "in place (reads only); fresh: the logits are restored in front of every launch and the restoring copy, "
+             "captured alone, is subtracted. `lsa_logit_process` runs the equivalent dense automaton "
+             "(`to_token_automaton`) on the same logits in the same process; both produced the same bits.", "",
+             "| kernel | pattern | states | table | walk | rows | allowed | steady us | fresh us | fresh spread us |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in out["kernel"]:
+        lines.append(f"| {r['kernel']} | `{r['pattern']}` | {r['states']} | {r['table_KB']} KB | {r['path']} | {r['rows']} | "
+                     f"{r['allowed']} | {r['steady_graphed_us']} | {r['fresh_graphed_us']} | {r['fresh_spread_us']} |")
+    if out["tpot"]:
+        lines += ["", "Step time of a 7B-shaped `SamplingDecodeGraph` (temperature 0.7, top-p 0.9), alternating windows of "
+                  "20 replays in one process, median of 5: without `grammar=`, with it and no regex row (every row "
+                  "skipped), and with every row under the permissive and the tight pattern.", "",
+                  "| layers | rows | sampling ms | grammar, no regex row ms | permissive ms | tight ms | spreads ms |",
+                  "|---|---|---|---|---|---|---|"]
+        for r in out["tpot"]:
+            lines.append(f"| {r['layers']} | {r['rows']} | {r['sampling_ms']} | {r['grammar_idle_ms']} "
+                         f"({r['grammar_idle_delta_ms']:+}) | {r['permissive_ms']} ({r['permissive_delta_ms']:+}) | "
+                         f"{r['tight_ms']} ({r['tight_delta_ms']:+}) | {r['sampling_spread_ms']} / {r['grammar_idle_spread_ms']} / "
+                         f"{r['permissive_spread_ms']} / {r['tight_spread_ms']} |")
+    return "\n".join(lines) + "\n"
+
+
+def main_grammar(a) -> dict:
+    out = {"kernel": [], "tpot": [], "lds_states": G.lds_states(), "threads": G.block_threads()}
+    vocab = synthetic_vocab()
+    edges = sorted({G.lds_states(), G.lds_states(alt=True)})
+    pats = ("-?[0-9]{1,6}", "[ -~]*") + tuple("[ -~]{0,%d}" % n for L in edges for n in (L - 1, L))
+    for rows in (1, 512):
+        for p in pats:
+            for r in bench_grammar_mask(rows, p, vocab):
+                out["kernel"].append(r)
+                print(json.dumps(r), flush=True)
+    if not a.skip_tpot:
+        for rows in (1, 512):
+            r = bench_tpot_grammar(a.layers, rows, vocab)
+            out["tpot"].append(r)
+            print(json.dumps(r), flush=True)
+    if a.md_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.md_out)), exist_ok=True)
+        with open(a.md_out, "w") as f:
+            f.write(grammar_markdown(out))
+    return out
+
+
 def main_constraints(a) -> dict:
     out = {"kernel": [], "tpot": []}
     for rows in (1, 512):
@@ -430,13 +628,16 @@ def main():
     ap.add_argument("--logprobs", action="store_true", help="measure lsa_logprobs and the step with logprobs=5 instead")
     ap.add_argument("--constraints", action="store_true",
                     help="measure lsa_logit_process and the step under choices instead")
+    ap.add_argument("--grammar", action="store_true",
+                    help="measure lsa_grammar_mask, the dense automaton beside it and the step under a regex instead")
+    ap.add_argument("--md-out", default="profiles/grammar_mask.md", help="--grammar: where its table goes")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sampling.py measures on the GPU: none found")
-    special = a.penalties or a.logprobs or a.constraints
+    special = a.penalties or a.logprobs or a.constraints or a.grammar
     out = (main_penalties(a) if a.penalties else main_logprobs(a) if a.logprobs else
-           main_constraints(a) if a.constraints else {"kernel": [], "tpot": []})
+           main_constraints(a) if a.constraints else main_grammar(a) if a.grammar else {"kernel": [], "tpot": []})
     for V in (() if a.skip_kernel or special else (32000, 128256)):
         for rows in (1, 128, 512):
             for mode in ("temperature", "top_k", "top_p"):

@@ -26,7 +26,9 @@ keys penalise repeated tokens on the device (also at temperature 0; one stage on
 ``logprobs`` key (0..20) adds a ``"logprobs"`` dict to the reply: per-token ``token_logprobs``,
 ``ranks`` and that many ``top_logprobs`` alternatives (one stage only); ``logit_bias``,
 ``banned_token_ids``, ``min_tokens``, ``min_p``, ``allowed_token_ids`` and ``choices`` keys constrain
-the output on the device (one stage only; ``--state-rows`` sizes the automaton arena);
+the output on the device (one stage only; ``--state-rows`` sizes the automaton arena); a ``regex``
+key makes the output's bytes fully match a pattern (one stage only; ``--dfa-rows`` sizes the
+byte-level DFA arena; ``--regex PATTERN`` does the same for every request of the load test);
 ``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty
 --logprobs --min-p --min-tokens`` do the same for the synthetic load test (request i seeded with
 ``--seed`` + i).
@@ -87,12 +89,22 @@ def main():
     ap.add_argument("--state-rows", type=int, default=256,
                     help="rows of the automaton arena of constrained requests (one per automaton state; allocated "
                          "with the first constrained request: 16 MB at V = 32000, 66 MB at V = 128256 for 256)")
+    ap.add_argument("--regex", default=None, metavar="PATTERN",
+                    help="load test: every request's output, as bytes, fully matches PATTERN (one stage only)")
+    ap.add_argument("--dfa-rows", type=int, default=4096, metavar="N",
+                    help="rows of the byte-level DFA arena of requests with a regex (one per DFA state, 512 B each "
+                         "whatever the vocabulary; allocated with the first such request)")
     ap.add_argument("--prefix-slots", type=int, default=0, metavar="P",
                     help="KV slots of the prefix pool (0: no prefix caching, no parallel samples)")
     ap.add_argument("--shared-prefix-len", type=int, default=0, metavar="L",
                     help="load test: every request starts with the same L tokens and declares them")
     ap.add_argument("--n", type=int, default=1, metavar="N", help="load test: N samples per prompt (submit_n)")
-    a = ap.parse_args()
+    argv = sys.argv[1:]
+    for i in range(len(argv) - 1):  # a pattern that starts with '-' is no option
+        if argv[i] == "--regex":
+            argv[i:i + 2] = ["--regex=" + argv[i + 1]]
+            break
+    a = ap.parse_args(argv)
     if a.random:
         a.model = a.random
     rc = RuntimeConfig.from_args(a)
@@ -137,10 +149,27 @@ def main():
     st = plan.stages[rank]
     if rank == 0:
         log.info(f"{cfg.name}: {world} stage(s) {plan.ranges()}, {M} x {rc.batch} slots")
+    # the tokenizer of the shards (the synthetic byte tokenizer for random weights) and, on a
+    # single-stage server, the byte strings of its vocabulary: what a request with a regex needs
+    tok = vocab_bytes = None
+    if rank == 0:
+        from llm_sharding_amd.models.tokenizer import SyntheticByteTokenizer, load_tokenizer
+        try:
+            tok = load_tokenizer(rc.shards) if rc.shards else None
+        except Exception as e:  # noqa: BLE001
+            log.warning(f"no tokenizer: {e}")
+        if world == 1:
+            from llm_sharding_amd.ops.grammar import VocabBytes
+            try:
+                vocab_bytes = VocabBytes.from_tokenizer(tok if tok is not None else SyntheticByteTokenizer(cfg.vocab_size),
+                                                        cfg.vocab_size)
+            except Exception as e:  # noqa: BLE001 - requests with a regex are then refused one by one
+                log.warning(f"no byte strings of the vocabulary: {e}")
     srv = PipelineServer(cfg, source, rank, world, st.start, st.end, dev, batch=rc.batch, microbatches=M,
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
-                         streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows)
+                         streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows,
+                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows)
     if rank != 0:
         srv.serve()
     elif a.requests:
@@ -151,10 +180,11 @@ def main():
             pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
             kw = {}
             if (a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None or a.min_p is not None
-                    or a.min_tokens):
+                    or a.min_tokens or a.regex is not None):
                 from llm_sharding_amd.runtime.sampling import SamplingParams
                 kw["sampling"] = SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i * a.n, *pen,
-                                                logprobs=a.logprobs, min_p=a.min_p, min_tokens=a.min_tokens)
+                                                logprobs=a.logprobs, min_p=a.min_p, min_tokens=a.min_tokens,
+                                                regex=a.regex)
             if a.n > 1:
                 srv.submit_n(ids, a.n, rc.max_new_tokens, eos_ids=(), **kw)
             elif shared and a.prefix_slots:
@@ -171,12 +201,6 @@ def main():
                   "slots": rc.batch * M, "microbatches": M})
         print(json.dumps(s), flush=True)
     else:
-        tok = None
-        try:
-            from llm_sharding_amd.models.tokenizer import load_tokenizer
-            tok = load_tokenizer(rc.shards) if rc.shards else None
-        except Exception as e:  # noqa: BLE001
-            log.warning(f"no tokenizer: {e}")
         stop_evt = threading.Event()
         th = threading.Thread(target=_ingress, args=(srv, rc.port, tok, stop_evt, rc.max_new_tokens), daemon=True)
         th.start()
