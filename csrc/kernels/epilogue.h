@@ -51,10 +51,12 @@ struct EpiArgs {
 
 LSA_DEVICE float silu(float g) { return g / (1.0f + __expf(-g)); }
 
-// 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))), tanh(u) = 1 - 2 / (exp(2u) + 1)
+// 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3), as x / (1 + exp(-2u)): the form
+// 0.5 x (2 - 2 / (exp(2u) + 1)) subtracts two numbers near 2 for negative x and loses the whole
+// result below x = -5. u = +-inf gives x / -0.
 LSA_DEVICE float gelu_tanh(float x) {
   const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-  return 0.5f * x * (2.0f - 2.0f / (__expf(2.0f * u) + 1.0f));
+  return x / (1.0f + __expf(-2.0f * u));
 }
 
 LSA_DEVICE float epi_bias(const EpiArgs& ep, int col) { return ep.bias ? ep.bias[col] : 0.f; }
