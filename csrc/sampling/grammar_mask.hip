@@ -54,7 +54,7 @@
 // (its size is read off the 'last row' bits of accept) is staged into LDS and walked there; a larger
 // one is walked from global memory (L2), 1.7 x slower. lsa_grammar_mask_alt is the same kernel with
 // the other threshold that was measured.
-#include "../kernels/common.h"
+#include "row_scan.h"
 
 namespace {
 
@@ -67,7 +67,6 @@ constexpr int GM_REG_WORDS = 8;           // the allow bits of 32 chunks per lan
 constexpr int GM_MAX_CHUNKS = GM_REG_WORDS * 4;
 constexpr int GM_MAX_V = GM_MAX_CHUNKS * GM_WAVES * GM_CHUNK - 8;
 constexpr int GM_EOS_MAX = 8;
-constexpr unsigned GM_NEG_INF = 0xFF80u;  // bf16 -inf
 
 long long g_grammar_mask_calls = 0;
 
@@ -191,8 +190,8 @@ LSA_DEVICE void gm_row(bf16_raw* __restrict__ row, int V, const short* tab, int 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned l0 = lv[j] & 0xffffu, l1 = lv[j] >> 16;
-        if (!(bits >> (2 * j) & 1u) && l0 != GM_NEG_INF) { l0 = GM_NEG_INF; ch = true; }
-        if (!(bits >> (2 * j + 1) & 1u) && l1 != GM_NEG_INF) { l1 = GM_NEG_INF; ch = true; }
+        if (!(bits >> (2 * j) & 1u) && l0 != BF16_NEG_INF) { l0 = BF16_NEG_INF; ch = true; }
+        if (!(bits >> (2 * j + 1) & 1u) && l1 != BF16_NEG_INF) { l1 = BF16_NEG_INF; ch = true; }
         lv[j] = l0 | (l1 << 16);
       }
       if (ch) st16(row + v0, lv);
@@ -200,7 +199,7 @@ LSA_DEVICE void gm_row(bf16_raw* __restrict__ row, int V, const short* tab, int 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int v = v0 + j;
-        if (v >= 0 && v < V && !(bits >> j & 1u) && row[v] != (bf16_raw)GM_NEG_INF) row[v] = (bf16_raw)GM_NEG_INF;
+        if (v >= 0 && v < V && !(bits >> j & 1u) && row[v] != (bf16_raw)BF16_NEG_INF) row[v] = (bf16_raw)BF16_NEG_INF;
       }
     }
   }

@@ -48,17 +48,16 @@
 // 8 x 512 vectors (V <= 32768) stays in registers between the two (eight vectors per thread, indexed
 // at compile time only) and is stored once; a longer or unaligned row is swept, stored and re-read
 // from L2, as lsa_sample's passes do. Both give the same bits (profiles/logit_process.md has the times).
-#include "../kernels/common.h"
+#include "row_scan.h"
 
 namespace {
 
-constexpr int LP_THREADS = 512;
-constexpr int LP_UNROLL = 4;
-constexpr int LP_BIAS_MAX = 320;
-constexpr int LP_EOS_MAX = 8;
-constexpr unsigned LP_NEG_INF = 0xFF80u;  // bf16 -inf
+constexpr int LGP_THREADS = 512;
+constexpr int LGP_UNROLL = 4;
+constexpr int LGP_BIAS_MAX = 320;
+constexpr int LGP_EOS_MAX = 8;
 
-constexpr int LP_REG_VECS = 8;            // min-p in registers: rows of up to 8 x 512 vectors (V <= 32768)
+constexpr int LGP_REG_VECS = 8;            // min-p in registers: rows of up to 8 x 512 vectors (V <= 32768)
 
 long long g_logit_process_calls = 0;
 
@@ -71,8 +70,8 @@ LSA_DEVICE float lp_mask8(u32x4_t& lv, const u32x4_t av, bool* ch) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     unsigned l0 = lv[j] & 0xffffu, l1 = lv[j] >> 16;
-    if ((av[j] & 0x8000u) && l0 != LP_NEG_INF) { l0 = LP_NEG_INF; *ch = true; }
-    if ((av[j] & 0x80000000u) && l1 != LP_NEG_INF) { l1 = LP_NEG_INF; *ch = true; }
+    if ((av[j] & 0x8000u) && l0 != BF16_NEG_INF) { l0 = BF16_NEG_INF; *ch = true; }
+    if ((av[j] & 0x80000000u) && l1 != BF16_NEG_INF) { l1 = BF16_NEG_INF; *ch = true; }
     lv[j] = l0 | (l1 << 16);
     m = fmaxf(m, fmaxf(bf2f((bf16_raw)l0), bf2f((bf16_raw)l1)));
   }
@@ -85,8 +84,8 @@ LSA_DEVICE bool lp_thr8(u32x4_t& lv, float thr) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     unsigned l0 = lv[j] & 0xffffu, l1 = lv[j] >> 16;
-    if (bf2f((bf16_raw)l0) < thr && l0 != LP_NEG_INF) { l0 = LP_NEG_INF; ch = true; }
-    if (bf2f((bf16_raw)l1) < thr && l1 != LP_NEG_INF) { l1 = LP_NEG_INF; ch = true; }
+    if (bf2f((bf16_raw)l0) < thr && l0 != BF16_NEG_INF) { l0 = BF16_NEG_INF; ch = true; }
+    if (bf2f((bf16_raw)l1) < thr && l1 != BF16_NEG_INF) { l1 = BF16_NEG_INF; ch = true; }
     lv[j] = l0 | (l1 << 16);
   }
   return ch;
@@ -100,11 +99,11 @@ LSA_DEVICE float lp_block_max(float m, float* sh_max) {
   __syncthreads();
   m = sh_max[0];
 #pragma unroll
-  for (int w = 1; w < LP_THREADS / LSA_WAVE; ++w) m = fmaxf(m, sh_max[w]);
+  for (int w = 1; w < LGP_THREADS / LSA_WAVE; ++w) m = fmaxf(m, sh_max[w]);
   return m;
 }
 
-__global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
+__global__ __launch_bounds__(LGP_THREADS) void logit_process_kernel(
     bf16_raw* __restrict__ logits, long long ld, int V, const int* __restrict__ slot, int n_slots,
     const int* __restrict__ tokens_in, const int* __restrict__ ctr, int ctr_add,
     const unsigned short* __restrict__ arena, long long ld_arena, int state_rows, int* __restrict__ astate,
@@ -112,13 +111,13 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
     const float* __restrict__ bias_val, const int* __restrict__ min_until, const float* __restrict__ minp_delta,
     int* __restrict__ fault, const int* __restrict__ eos, int reread) {
   __shared__ int sh_a;
-  __shared__ float sh_max[LP_THREADS / LSA_WAVE];
+  __shared__ float sh_max[LGP_THREADS / LSA_WAVE];
   const int r = blockIdx.x, tid = threadIdx.x;
   const int s = slot[r];
   if (s < 0 || s >= n_slots) return;
   const int c = ctr[r] + ctr_add;
   const int a0 = astate[s];
-  const int bn = min(max(bias_n[s], 0), LP_BIAS_MAX);
+  const int bn = min(max(bias_n[s], 0), LGP_BIAS_MAX);
   const bool eos_on = c < min_until[s];
   const float delta = minp_delta[s];
   const bool minp = delta > lp_neg_inf();
@@ -148,19 +147,19 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
   }
   // 2a. bias entries and EOS ids, one thread each
   if (tid < bn) {
-    const int v = bias_tok[(size_t)s * LP_BIAS_MAX + tid];
+    const int v = bias_tok[(size_t)s * LGP_BIAS_MAX + tid];
     if (v >= 0 && v < V) {
       bool is_eos = false;
       if (eos_on) {
 #pragma unroll
-        for (int j = 0; j < LP_EOS_MAX; ++j) is_eos |= eos[j] == v;
+        for (int j = 0; j < LGP_EOS_MAX; ++j) is_eos |= eos[j] == v;
       }
-      const float x = bf2f(row[v]) + bias_val[(size_t)s * LP_BIAS_MAX + tid];
-      row[v] = is_eos ? (bf16_raw)LP_NEG_INF : f2bf(x);
+      const float x = bf2f(row[v]) + bias_val[(size_t)s * LGP_BIAS_MAX + tid];
+      row[v] = is_eos ? (bf16_raw)BF16_NEG_INF : f2bf(x);
     }
-  } else if (eos_on && tid >= LP_BIAS_MAX && tid < LP_BIAS_MAX + LP_EOS_MAX) {
-    const int v = eos[tid - LP_BIAS_MAX];
-    if (v >= 0 && v < V) row[v] = (bf16_raw)LP_NEG_INF;
+  } else if (eos_on && tid >= LGP_BIAS_MAX && tid < LGP_BIAS_MAX + LGP_EOS_MAX) {
+    const int v = eos[tid - LGP_BIAS_MAX];
+    if (v >= 0 && v < V) row[v] = (bf16_raw)BF16_NEG_INF;
   }
   __syncthreads();
   const int a = sh_a;
@@ -171,21 +170,21 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
   const size_t align = reinterpret_cast<size_t>(row) | (arow ? reinterpret_cast<size_t>(arow) : 0);
   const int nvec = (align & 15) == 0 ? (V >> 3) : 0;
   float m = lp_neg_inf();
-  if (minp && !reread && nvec > 0 && nvec <= LP_REG_VECS * LP_THREADS) {
+  if (minp && !reread && nvec > 0 && nvec <= LGP_REG_VECS * LGP_THREADS) {
     // min-p with the row kept in registers (compile-time indexing only): one trip over the row
-    u32x4_t lv[LP_REG_VECS], av[LP_REG_VECS];
+    u32x4_t lv[LGP_REG_VECS], av[LGP_REG_VECS];
     unsigned chm = 0u;
 #pragma unroll
-    for (int u = 0; u < LP_REG_VECS; ++u) {
-      const int cv = tid + u * LP_THREADS;
+    for (int u = 0; u < LGP_REG_VECS; ++u) {
+      const int cv = tid + u * LGP_THREADS;
       if (cv < nvec) {
         lv[u] = ld16(row + (size_t)cv * 8);
         av[u] = arow ? ld16(arow + (size_t)cv * 8) : u32x4_t{0u, 0u, 0u, 0u};
       }
     }
 #pragma unroll
-    for (int u = 0; u < LP_REG_VECS; ++u) {
-      if (tid + u * LP_THREADS < nvec) {
+    for (int u = 0; u < LGP_REG_VECS; ++u) {
+      if (tid + u * LGP_THREADS < nvec) {
         bool ch = false;
         m = fmaxf(m, lp_mask8(lv[u], av[u], &ch));
         chm |= ch ? 1u << u : 0u;
@@ -195,37 +194,37 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
     const int ti = nvec * 8 + tid;  // the V % 8 tail: at most one column per thread
     if (ti < V) {
       tl = row[ti];
-      if (arow && (arow[ti] & 0x8000u)) tl = LP_NEG_INF;
+      if (arow && (arow[ti] & 0x8000u)) tl = BF16_NEG_INF;
       m = fmaxf(m, bf2f((bf16_raw)tl));
     }
     const float thr = lp_block_max(m, sh_max) + delta;
 #pragma unroll
-    for (int u = 0; u < LP_REG_VECS; ++u) {
-      const int cv = tid + u * LP_THREADS;
+    for (int u = 0; u < LGP_REG_VECS; ++u) {
+      const int cv = tid + u * LGP_THREADS;
       if (cv < nvec) {
         const bool ch = lp_thr8(lv[u], thr);
         if (ch || (chm >> u & 1u)) st16(row + (size_t)cv * 8, lv[u]);
       }
     }
     if (ti < V) {
-      if (bf2f((bf16_raw)tl) < thr) tl = LP_NEG_INF;
+      if (bf2f((bf16_raw)tl) < thr) tl = BF16_NEG_INF;
       if (tl != row[ti]) row[ti] = (bf16_raw)tl;
     }
     return;
   }
-  for (int c0 = tid; c0 < nvec; c0 += LP_UNROLL * LP_THREADS) {
-    u32x4_t lv[LP_UNROLL], av[LP_UNROLL];
+  for (int c0 = tid; c0 < nvec; c0 += LGP_UNROLL * LGP_THREADS) {
+    u32x4_t lv[LGP_UNROLL], av[LGP_UNROLL];
 #pragma unroll
-    for (int u = 0; u < LP_UNROLL; ++u) {
-      const int cv = c0 + u * LP_THREADS;
+    for (int u = 0; u < LGP_UNROLL; ++u) {
+      const int cv = c0 + u * LGP_THREADS;
       if (cv < nvec) {
         lv[u] = ld16(row + (size_t)cv * 8);
         av[u] = arow ? ld16(arow + (size_t)cv * 8) : u32x4_t{0u, 0u, 0u, 0u};
       }
     }
 #pragma unroll
-    for (int u = 0; u < LP_UNROLL; ++u) {
-      const int cv = c0 + u * LP_THREADS;
+    for (int u = 0; u < LGP_UNROLL; ++u) {
+      const int cv = c0 + u * LGP_THREADS;
       if (cv < nvec) {
         bool ch = false;
         m = fmaxf(m, lp_mask8(lv[u], av[u], &ch));
@@ -233,10 +232,10 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
       }
     }
   }
-  for (int i = nvec * 8 + tid; i < V; i += LP_THREADS) {
+  for (int i = nvec * 8 + tid; i < V; i += LGP_THREADS) {
     unsigned l = row[i];
-    if (arow && (arow[i] & 0x8000u) && l != LP_NEG_INF) {
-      l = LP_NEG_INF;
+    if (arow && (arow[i] & 0x8000u) && l != BF16_NEG_INF) {
+      l = BF16_NEG_INF;
       row[i] = (bf16_raw)l;
     }
     m = fmaxf(m, bf2f((bf16_raw)l));
@@ -245,22 +244,22 @@ __global__ __launch_bounds__(LP_THREADS) void logit_process_kernel(
 
   // 3. min-p: the row maximum, then every value below it by more than |delta|
   const float thr = lp_block_max(m, sh_max) + delta;
-  for (int c0 = tid; c0 < nvec; c0 += LP_UNROLL * LP_THREADS) {
-    u32x4_t lv[LP_UNROLL];
+  for (int c0 = tid; c0 < nvec; c0 += LGP_UNROLL * LGP_THREADS) {
+    u32x4_t lv[LGP_UNROLL];
 #pragma unroll
-    for (int u = 0; u < LP_UNROLL; ++u) {
-      const int cv = c0 + u * LP_THREADS;
+    for (int u = 0; u < LGP_UNROLL; ++u) {
+      const int cv = c0 + u * LGP_THREADS;
       if (cv < nvec) lv[u] = ld16(row + (size_t)cv * 8);
     }
 #pragma unroll
-    for (int u = 0; u < LP_UNROLL; ++u) {
-      const int cv = c0 + u * LP_THREADS;
+    for (int u = 0; u < LGP_UNROLL; ++u) {
+      const int cv = c0 + u * LGP_THREADS;
       if (cv < nvec && lp_thr8(lv[u], thr)) st16(row + (size_t)cv * 8, lv[u]);
     }
   }
-  for (int i = nvec * 8 + tid; i < V; i += LP_THREADS) {
+  for (int i = nvec * 8 + tid; i < V; i += LGP_THREADS) {
     const unsigned l = row[i];
-    if (bf2f((bf16_raw)l) < thr && l != LP_NEG_INF) row[i] = (bf16_raw)LP_NEG_INF;
+    if (bf2f((bf16_raw)l) < thr && l != BF16_NEG_INF) row[i] = (bf16_raw)BF16_NEG_INF;
   }
 }
 
@@ -279,7 +278,7 @@ int logit_process_launch(void* logits, long long ld, int V, int rows, const int*
   if (!logits || !slot || !ctr || !arena || !astate || !abase || !bias_n || !bias_tok || !bias_val || !min_until ||
       !minp_delta || !fault || !eos)
     return LSA_BAD_SHAPE;
-  logit_process_kernel<<<rows, LP_THREADS, 0, stream>>>(
+  logit_process_kernel<<<rows, LGP_THREADS, 0, stream>>>(
       static_cast<bf16_raw*>(logits), ld, V, slot, n_slots, tokens_in, ctr, ctr_add,
       static_cast<const unsigned short*>(arena), ld_arena, state_rows, astate, abase, bias_n, bias_tok, bias_val,
       min_until, minp_delta, fault, eos, reread);

@@ -36,83 +36,12 @@
 // V - 1 has bytes) pick the lowest indices. All composites are distinct, so exactly n entries lie
 // at or above the threshold; they are collected into LDS and ordered by rank counting. The row
 // is re-read from L2 per pass: 2 passes for n = 0, 3 for n > 0, + 1 per index level on ties.
-#include "../kernels/common.h"
+#include "row_scan.h"
 
 namespace {
 
 constexpr int LP_THREADS = 512;
 constexpr int LP_TOP_MAX = 20;
-
-// Order-preserving key of a bf16 pattern (larger value -> larger key); -0 counts as +0.
-LSA_DEVICE unsigned lp_key16(unsigned raw) {
-  if (raw == 0x8000u) raw = 0u;
-  return (raw & 0x8000u) ? (~raw & 0xffffu) : (raw | 0x8000u);
-}
-LSA_DEVICE unsigned lp_raw_of_key16(unsigned k) { return (k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu); }
-
-// f(index, raw bf16) for every column < V of the row: 16-byte loads over the 8-aligned body
-// when the row starts 16-byte aligned, scalar loads otherwise and for the tail.
-template <typename F>
-LSA_DEVICE void lp_for_row(const bf16_raw* __restrict__ row, int V, F&& f) {
-  const int tid = threadIdx.x;
-  const int nvec = ((reinterpret_cast<size_t>(row) & 15) == 0) ? (V >> 3) : 0;
-  for (int c = tid; c < nvec; c += LP_THREADS) {
-    const u32x4_t v = ld16(row + (size_t)c * 8);
-    const unsigned w[4] = {v[0], v[1], v[2], v[3]};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f(c * 8 + 2 * j, w[j] & 0xffffu);
-      f(c * 8 + 2 * j + 1, w[j] >> 16);
-    }
-  }
-  for (int i = nvec * 8 + tid; i < V; i += LP_THREADS) f(i, (unsigned)row[i]);
-}
-
-// Wave 0: the largest bin b of h[0..256) with  base + sum_{j >= b} h[j] >= target, written to
-// out[0] = b, out[1] = base + sum_{j > b} h[j], out[2] = h[b]. target >= 1; if even bin 0 does
-// not reach it (cannot happen for a target <= base + the total) bin 0 is returned.
-LSA_DEVICE void lp_find_bin(const unsigned* h, unsigned base, unsigned target, unsigned* out) {
-  const int lane = threadIdx.x;  // called by threads 0..63
-  unsigned v[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[j] = h[4 * lane + j];
-    s += v[j];
-  }
-  unsigned suf = s;  // sum over lanes >= lane
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_down(suf, o, 64);
-    if (lane + o < 64) suf += t;
-  }
-  unsigned acc = base + (suf - s), above = 0, at = 0;
-  int b = -1;
-#pragma unroll
-  for (int j = 3; j >= 0; --j) {
-    const unsigned a0 = acc;
-    acc += v[j];
-    if (b < 0 && acc >= target) {
-      b = 4 * lane + j;
-      above = a0;
-      at = v[j];
-    }
-  }
-  const unsigned long long found = __ballot(b >= 0);
-  if (found == 0ull) {
-    if (lane == 0) {
-      out[0] = 0u;
-      out[1] = acc - v[0];
-      out[2] = v[0];
-    }
-    return;
-  }
-  const int top = 63 - __clzll((long long)found);
-  if (lane == top) {
-    out[0] = (unsigned)b;
-    out[1] = above;
-    out[2] = at;
-  }
-}
 
 __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
     const bf16_raw* __restrict__ logits, long long ld, int V, const int* __restrict__ n_top,
@@ -132,7 +61,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   const bf16_raw* row = logits + (size_t)r * (size_t)ld;
   const int t = target[r];
   const bool has_t = t >= 0 && t < V;
-  const unsigned kt = has_t ? lp_key16((unsigned)row[t]) : 0xffffu;
+  const unsigned kt = has_t ? key16((unsigned)row[t]) : 0xffffu;
 
   // pass 1: maximum key, the target's rank and (n > 0) the count histogram of the high bytes
   if (tid < 256) s_cnt[tid] = 0u;
@@ -144,8 +73,8 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   }
   __syncthreads();
   unsigned kbest = 0u, above_t = 0u;
-  lp_for_row(row, V, [&](int, unsigned raw) {
-    const unsigned k = lp_key16(raw);
+  for_row<LP_THREADS>(row, V, [&](int, unsigned raw) {
+    const unsigned k = key16(raw);
     kbest = k > kbest ? k : kbest;
     above_t += k > kt ? 1u : 0u;
     if (n > 0) atomicAdd(&s_cnt[k >> 8], 1u);
@@ -162,11 +91,11 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   }
   __syncthreads();
   const unsigned kmax = s_kmax;
-  const float lmax = bf2f((bf16_raw)lp_raw_of_key16(kmax));
+  const float lmax = bf2f((bf16_raw)raw_of_key16(kmax));
 
   unsigned hb = 0u, above = 0u;
   if (n > 0) {
-    if (tid < 64) lp_find_bin(s_cnt, 0u, (unsigned)n, s_find);
+    if (tid < 64) find_bin<true>(s_cnt, 0u, (unsigned)n, s_find);
     __syncthreads();
     hb = s_find[0];
     above = s_find[1];
@@ -177,11 +106,11 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
 
   // pass 2: the fixed-point mass and (n > 0) the low-byte histogram inside the boundary bin
   unsigned long long mass = 0ull;
-  lp_for_row(row, V, [&](int, unsigned raw) {
+  for_row<LP_THREADS>(row, V, [&](int, unsigned raw) {
     const float w = expf(bf2f((bf16_raw)raw) - lmax);
     mass += (unsigned long long)(w * 4294967296.0f);
     if (n > 0) {
-      const unsigned k = lp_key16(raw);
+      const unsigned k = key16(raw);
       if ((k >> 8) == hb) atomicAdd(&s_cnt[k & 255u], 1u);
     }
   });
@@ -194,7 +123,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   if (tid == 0) {
     lse[r] = lmax + lnS;
     if (has_t) {
-      const float lp = (bf2f((bf16_raw)lp_raw_of_key16(kt)) - lmax) - lnS;
+      const float lp = (bf2f((bf16_raw)raw_of_key16(kt)) - lmax) - lnS;
       tok_lp[r] = lp;
       tok_rank[r] = (int)s_rank + 1;
       if (lp_hist) {  // beside the token history: lsa_argmax_finalize has already advanced the counter
@@ -213,7 +142,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   if (n == 0) return;
 
   // threshold key tk = the n-th largest key; `above` entries are strictly larger
-  if (tid < 64) lp_find_bin(s_cnt, above, (unsigned)n, s_find);
+  if (tid < 64) find_bin<true>(s_cnt, above, (unsigned)n, s_find);
   __syncthreads();
   const unsigned tk = (hb << 8) | s_find[0];
   above = s_find[1];
@@ -230,15 +159,15 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
       const int sh = 8 * level;
       if (tid < 256) s_cnt[tid] = 0u;
       __syncthreads();
-      lp_for_row(row, V, [&](int i, unsigned raw) {
-        if (lp_key16(raw) == tk) {
+      for_row<LP_THREADS>(row, V, [&](int i, unsigned raw) {
+        if (key16(raw) == tk) {
           const unsigned q = vm - (unsigned)i;
           // bytes above this level match the prefix found so far (sh + 8 == 32: no such bytes)
           if (level == 3 || (q >> (sh + 8)) == (qthr >> (sh + 8))) atomicAdd(&s_cnt[(q >> sh) & 255u], 1u);
         }
       });
       __syncthreads();
-      if (tid < 64) lp_find_bin(s_cnt, above, (unsigned)n, s_find);
+      if (tid < 64) find_bin<true>(s_cnt, above, (unsigned)n, s_find);
       __syncthreads();
       qthr |= s_find[0] << sh;
       above = s_find[1];
@@ -247,8 +176,8 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
   }
 
   // collect the n winners (composite >= (tk, qthr)) and order them by rank counting
-  lp_for_row(row, V, [&](int i, unsigned raw) {
-    const unsigned k = lp_key16(raw), q = (unsigned)(V - 1) - (unsigned)i;
+  for_row<LP_THREADS>(row, V, [&](int i, unsigned raw) {
+    const unsigned k = key16(raw), q = (unsigned)(V - 1) - (unsigned)i;
     if (k > tk || (k == tk && q >= qthr)) {
       const unsigned slot = atomicAdd(&s_n, 1u);
       if (slot < (unsigned)LP_TOP_MAX) s_list[slot] = ((unsigned long long)k << 32) | (unsigned long long)q;
@@ -262,7 +191,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprobs_kernel(
     for (int j = 0; j < got; ++j) rank += s_list[j] > c ? 1 : 0;
     const unsigned k = (unsigned)(c >> 32), q = (unsigned)(c & 0xffffffffull);
     top_id[(size_t)r * LP_TOP_MAX + rank] = (int)((unsigned)(V - 1) - q);
-    top_lp[(size_t)r * LP_TOP_MAX + rank] = (bf2f((bf16_raw)lp_raw_of_key16(k)) - lmax) - lnS;
+    top_lp[(size_t)r * LP_TOP_MAX + rank] = (bf2f((bf16_raw)raw_of_key16(k)) - lmax) - lnS;
   }
 }
 

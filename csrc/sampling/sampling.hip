@@ -25,7 +25,7 @@
 // inside the boundary bin). Counts are integers and masses are exp((l - max) / T) as 32-bit
 // fixed point summed by 64-bit integer LDS atomics: sums do not depend on arrival order, so the
 // same inputs give bitwise the same token on every launch. The row is re-read from L2 per pass.
-#include "../kernels/common.h"
+#include "row_scan.h"
 
 namespace {
 
@@ -57,33 +57,6 @@ LSA_DEVICE float gumbel_from_bits(unsigned x) {
   return -logf(-logf(u));
 }
 
-// ---------------------------------------------------------------------------- 16-bit keys
-// Order-preserving key of a bf16 pattern (larger value -> larger key); -0 counts as +0, so
-// values that compare equal share one key.
-LSA_DEVICE unsigned key16(unsigned raw) {
-  if (raw == 0x8000u) raw = 0u;
-  return (raw & 0x8000u) ? (~raw & 0xffffu) : (raw | 0x8000u);
-}
-LSA_DEVICE unsigned raw_of_key16(unsigned k) { return (k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu); }
-
-// f(index, raw bf16) for every column < V of the row: 16-byte loads over the 8-aligned body
-// when the row starts 16-byte aligned, scalar loads otherwise and for the tail.
-template <typename F>
-LSA_DEVICE void for_row(const bf16_raw* __restrict__ row, int V, F&& f) {
-  const int tid = threadIdx.x;
-  const int nvec = ((reinterpret_cast<size_t>(row) & 15) == 0) ? (V >> 3) : 0;
-  for (int c = tid; c < nvec; c += SAMPLE_THREADS) {
-    const u32x4_t v = ld16(row + (size_t)c * 8);
-    const unsigned w[4] = {v[0], v[1], v[2], v[3]};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f(c * 8 + 2 * j, w[j] & 0xffffu);
-      f(c * 8 + 2 * j + 1, w[j] >> 16);
-    }
-  }
-  for (int i = nvec * 8 + tid; i < V; i += SAMPLE_THREADS) f(i, (unsigned)row[i]);
-}
-
 LSA_DEVICE unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -103,50 +76,6 @@ LSA_DEVICE unsigned long long block_max_u64(unsigned long long v, unsigned long 
 #pragma unroll
   for (int w = 1; w < SAMPLE_WAVES; ++w) m = s_red[w] > m ? s_red[w] : m;
   return m;
-}
-
-// Wave 0: the largest bin b of h[0..256) with  base + sum_{j >= b} h[j] >= target  and the sum
-// strictly above it, written to out[0] = b, out[1] = base + sum_{j > b} h[j]. target >= 1; if
-// even bin 0 does not reach it (cannot happen for a target <= the total) bin 0 is returned.
-template <typename T>
-LSA_DEVICE void find_bin(const T* h, unsigned long long base, unsigned long long target, unsigned long long* out) {
-  const int lane = threadIdx.x;  // called by threads 0..63
-  unsigned long long v[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[j] = (unsigned long long)h[4 * lane + j];
-    s += v[j];
-  }
-  unsigned long long suf = s;  // sum over lanes >= lane
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long t = __shfl_down(suf, o, 64);
-    if (lane + o < 64) suf += t;
-  }
-  unsigned long long acc = base + (suf - s), above = 0;
-  int b = -1;
-#pragma unroll
-  for (int j = 3; j >= 0; --j) {
-    const unsigned long long a0 = acc;
-    acc += v[j];
-    if (b < 0 && acc >= target) {
-      b = 4 * lane + j;
-      above = a0;
-    }
-  }
-  const unsigned long long found = __ballot(b >= 0);
-  if (found == 0ull) {
-    if (lane == 0) {
-      out[0] = 0ull;
-      out[1] = acc - v[0];
-    }
-    return;
-  }
-  const int top = 63 - __clzll((long long)found);
-  if (lane == top) {
-    out[0] = (unsigned long long)b;
-    out[1] = above;
-  }
 }
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
@@ -171,7 +100,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   if (tid == 0) s_kept = 0u;
   __syncthreads();
   unsigned long long best = 0ull;
-  for_row(row, V, [&](int i, unsigned raw) {
+  for_row<SAMPLE_THREADS>(row, V, [&](int i, unsigned raw) {
     const unsigned k = key16(raw);
     const unsigned long long kk = ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
     best = kk > best ? kk : best;
@@ -204,7 +133,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     __syncthreads();
     s_cnt[tid & 255] = 0u;
     __syncthreads();
-    for_row(row, V, [&](int, unsigned raw) {
+    for_row<SAMPLE_THREADS>(row, V, [&](int, unsigned raw) {
       const unsigned k = key16(raw);
       if ((k >> 8) == hb) atomicAdd(&s_cnt[k & 255u], 1u);
     });
@@ -221,7 +150,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   if (p < 1.f) {
     if (tid < 256) s_mass[tid] = 0ull;
     __syncthreads();
-    for_row(row, V, [&](int, unsigned raw) {
+    for_row<SAMPLE_THREADS>(row, V, [&](int, unsigned raw) {
       const unsigned k = key16(raw);
       if (k >= tk) {
         const float w = expf((bf2f((bf16_raw)raw) - lmax) / T);
@@ -247,7 +176,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     __syncthreads();
     if (tid < 256) s_mass[tid] = 0ull;
     __syncthreads();
-    for_row(row, V, [&](int, unsigned raw) {
+    for_row<SAMPLE_THREADS>(row, V, [&](int, unsigned raw) {
       const unsigned k = key16(raw);
       if (k >= tk && (k >> 8) == hb) {
         const float w = expf((bf2f((bf16_raw)raw) - lmax) / T);
@@ -269,7 +198,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   unsigned long long win = 0ull;
   unsigned kept = 0u, blk_cached = 0xffffffffu;
   Philox4 px = {};
-  for_row(row, V, [&](int i, unsigned raw) {
+  for_row<SAMPLE_THREADS>(row, V, [&](int i, unsigned raw) {
     if (key16(raw) >= thr) {
       ++kept;
       const unsigned blk = (unsigned)i >> 2;

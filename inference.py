@@ -294,45 +294,36 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out
     hidden): the first token from ``Sampler.sample``, the rest from a captured
     ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
     sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along, with a
-    constraint its ``ConstraintState``, with a regex its ``GrammarState`` over the byte strings of ``tok``'s
-    vocabulary. With
-    ``sp.logprobs`` the tokens' log-probabilities, ranks and alternatives go into the dict
-    ``lp_out`` (``lp``, ``rank``, ``top``: per token a list of (id, logprob))."""
-    from llm_sharding_amd.runtime.sampling import (ConstraintState, EagerSamplingDecode, GrammarState, PenaltyState,
-                                                   Sampler, SamplingDecodeGraph)
+    constraint its ``ConstraintState``, with a regex its ``GrammarState`` over the byte strings of
+    ``tok``'s vocabulary (``runtime.logit_stages``). With ``sp.logprobs`` the tokens'
+    log-probabilities, ranks and alternatives go into the dict ``lp_out`` (``lp``, ``rank``, ``top``:
+    per token a list of (id, logprob))."""
+    from llm_sharding_amd.ops.grammar import VocabBytes
+    from llm_sharding_amd.runtime.logit_stages import STAGE_CLASSES
+    from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, Sampler, SamplingDecodeGraph
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
-    pen, kw = None, {}
-    if sp.penalized:
-        print(f"[INFO] penalties: repetition {sp.repetition_penalty} presence {sp.presence_penalty} "
-              f"frequency {sp.frequency_penalty}")
-        pen = PenaltyState(eng, 1)
-        pen.admit(0, prompt_ids)
-        kw = {"penalties": pen}
-    con = None
-    if sp.constrained:
-        try:
-            con = ConstraintState(eng, 1, state_rows=max(1, sum(len(c) for c in sp.choices or ()) + 2))
-            con.admit(0, sp, n_prompt)
-        except ValueError as e:
-            raise SystemExit(f"[ERROR] {e}")
-        print(f"[INFO] constraints: {len(sp.bias_entries())} bias entries, min_tokens {sp.min_tokens}, "
-              f"min_p {sp.min_p}, {len(sp.choices or ())} choices")
-        kw["constraints"] = con
-    gram = None
-    if sp.grammar is not None:
-        from llm_sharding_amd.ops.grammar import VocabBytes
-        try:
-            gram = GrammarState(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size),
-                                dfa_rows=sp.grammar.n_states)
-            gram.admit(0, sp)
-        except ValueError as e:
-            raise SystemExit(f"[ERROR] {e}")
-        print(f"[INFO] regex {sp.regex!r}: a byte-level DFA of {sp.grammar.n_states} states")
-        kw["grammar"] = gram
+    build = {  # a one-slot state per stage the request asks for, and the line that reports it
+        "penalties": lambda cls: (cls(eng, 1), f"penalties: repetition {sp.repetition_penalty} presence "
+                                  f"{sp.presence_penalty} frequency {sp.frequency_penalty}"),
+        "constraints": lambda cls: (cls(eng, 1, state_rows=max(1, sum(len(c) for c in sp.choices or ()) + 2)),
+                                    f"constraints: {len(sp.bias_entries())} bias entries, min_tokens {sp.min_tokens}, "
+                                    f"min_p {sp.min_p}, {len(sp.choices or ())} choices"),
+        "grammar": lambda cls: (cls(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size),
+                                    dfa_rows=sp.grammar.n_states),
+                                f"regex {sp.regex!r}: a byte-level DFA of {sp.grammar.n_states} states"),
+    }
+    kw = {}
+    for cls in STAGE_CLASSES:
+        if cls.wants(sp):
+            try:
+                kw[cls.name], line = build[cls.name](cls)
+                kw[cls.name].enter(0, sp, prompt_ids)
+            except ValueError as e:
+                raise SystemExit(f"[ERROR] {e}")
+            print(f"[INFO] {line}")
     want_lp = sp.logprobs is not None
-    stateful = pen is not None or con is not None or gram is not None
-    first = Sampler(eng, pen, con, gram).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if stateful else None,
-                                                return_logprobs=want_lp)
+    first = Sampler(eng, **kw).sample(h, [n_prompt - 1], [sp], [n_prompt], slots=[0] if kw else None,
+                                      return_logprobs=want_lp)
     steps = []
     if want_lp:
         first, lp0 = first

@@ -54,6 +54,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from ..runtime.engine import DecodeGraph, StageEngine
+from ..runtime.logit_stages import STAGE_CLASSES, STAGE_ORDER, ordered_stages
 from ..runtime.sampling import SamplingParams
 from ..utils import tracing
 from .pipeline import DistP2P, _percentile
@@ -203,23 +204,16 @@ class PipelineServer:
         # server never builds a Sampler, a sampling graph or a logits buffer
         self.sampling_on = False
         self.sampler = None
-        # penalties: the per-slot token statistics exist from the first penalised request on
-        self.penalties = None
+        # logit stages (runtime.logit_stages): each one's tables exist, and the graphs carry its
+        # launch, from the first request that asks for it on - the penalties' token statistics, the
+        # constraints' automaton arena (state_rows rows), the DFA arena of a regex (dfa_rows rows of
+        # 512 B; vocab_bytes, an ops.grammar.VocabBytes, is what such requests need). The host
+        # allocators of the two arenas exist from the first such submit on.
+        self.penalties = self.constraints = self.grammar = None
+        self.state_rows, self.vocab_bytes, self.dfa_rows = int(state_rows), vocab_bytes, int(dfa_rows)
+        self._arena = self._garena = self._gcheck = None
         # logprobs: the graphs carry the lsa_logprobs launch from the first request that asks on
         self.logprobs_on = False
-        # constraints: the automaton arena (state_rows rows) and the per-slot tables exist, and the
-        # graphs carry the lsa_logit_process launch, from the first constrained request on; the
-        # host allocator of the arena's rows from the first constrained submit on
-        self.state_rows = int(state_rows)
-        self.constraints = None
-        self._arena = None
-        # regex: the DFA arena (dfa_rows rows of 512 B), the vocabulary's byte strings and the
-        # per-slot states exist, and the graphs carry the lsa_grammar_mask launch, from the first
-        # request with a regex on; vocab_bytes (ops.grammar.VocabBytes) is what such requests need
-        self.vocab_bytes, self.dfa_rows = vocab_bytes, int(dfa_rows)
-        self.grammar = None
-        self._garena = None
-        self._gcheck = None
         self._lp_out: List = [None] * microbatches  # logprobs of a micro-batch's outstanding command
         self._build_graphs()
         # rank 0 state
@@ -257,8 +251,7 @@ class PipelineServer:
                 if self.sampling_on:
                     from ..runtime.sampling import SamplingDecodeGraph
                     g = SamplingDecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S,
-                                            penalties=self.penalties, logprobs=self.logprobs_on,
-                                            constraints=self.constraints, grammar=self.grammar)
+                                            logprobs=self.logprobs_on, **self._stage_kw())
                 else:
                     g = DecodeGraph(self.eng, self.B, mode, slots=self._slots(mb), scratch=mb % self.S)
                 self.graphs.append(g.capture())
@@ -272,60 +265,46 @@ class PipelineServer:
         positions and tokens. Rows start greedy; a slot's parameters are written on admission.
         From here on greedy requests of this server take the arg-max of the bf16 logits in the
         decode graph (the first token still comes from the fused argmax)."""
-        from ..runtime.sampling import PenaltyState, Sampler
-        if penalties:  # the first non-greedy request is a penalised one: one rebuild for both
-            self.penalties = PenaltyState(self.eng, self.B * self.M)
-        if constraints:
-            self.constraints = self._new_constraints()
-        if grammar:
-            self.grammar = self._new_grammar()
+        from ..runtime.sampling import Sampler
+        first = {"penalties": penalties, "constraints": constraints, "grammar": grammar}
+        for name in STAGE_ORDER:  # the first non-greedy request asks for stages too: one rebuild for all
+            if first[name]:
+                setattr(self, name, self._new_stage(name))
         self.logprobs_on = self.logprobs_on or logprobs
-        self.sampler = Sampler(self.eng, self.penalties, self.constraints, self.grammar)
+        self.sampler = Sampler(self.eng, **self._stage_kw())
         self.sampling_on = True
         self._swap_sampling_graphs()
 
-    def _new_constraints(self):
+    def _stage_kw(self) -> dict:
+        """The logit stages (or None) by the keyword a Sampler or a graph takes them by."""
+        return {name: getattr(self, name) for name in STAGE_ORDER}
+
+    def _allocator(self, attr: str, rows: int):
+        """The host allocator of an arena's rows, kept in ``attr`` and created on first use."""
         from ..ops.constraints import ArenaAllocator
-        from ..runtime.sampling import ConstraintState
         with self._lock:
-            if self._arena is None:
-                self._arena = ArenaAllocator(self.state_rows)
-        return ConstraintState(self.eng, self.B * self.M, self.state_rows, allocator=self._arena)
+            if getattr(self, attr) is None:
+                setattr(self, attr, ArenaAllocator(rows))
+            return getattr(self, attr)
 
-    def _enable_constraints(self) -> None:
-        """First constrained request (sampling already on): allocate the ConstraintState and, in
-        graph mode, replace every sampling graph by one whose step runs ``lsa_logit_process``
-        between ``lsa_penalize`` and ``lsa_sample``, carrying positions, tokens and the rows'
-        parameters over. Until then no graph holds that kernel and no table is allocated."""
-        self.constraints = self._new_constraints()
-        self.sampler.constraints = self.constraints
-        self._swap_sampling_graphs()
+    def _new_stage(self, name: str):
+        from ..runtime import logit_stages as LS
+        n = self.B * self.M
+        return {
+            "penalties": lambda: LS.PenaltyState(self.eng, n),
+            "constraints": lambda: LS.ConstraintState(self.eng, n, self.state_rows,
+                                                      allocator=self._allocator("_arena", self.state_rows)),
+            "grammar": lambda: LS.GrammarState(self.eng, n, self.vocab_bytes, self.dfa_rows,
+                                               allocator=self._allocator("_garena", self.dfa_rows)),
+        }[name]()
 
-    def _new_grammar(self):
-        from ..ops.constraints import ArenaAllocator
-        from ..runtime.sampling import GrammarState
-        with self._lock:
-            if self._garena is None:
-                self._garena = ArenaAllocator(self.dfa_rows)
-        return GrammarState(self.eng, self.B * self.M, self.vocab_bytes, self.dfa_rows, allocator=self._garena)
-
-    def _enable_grammar(self) -> None:
-        """First request with a regex (sampling already on): allocate the GrammarState and, in graph
-        mode, replace every sampling graph by one whose step runs ``lsa_grammar_mask`` between
-        ``lsa_penalize`` and ``lsa_logit_process``, carrying positions, tokens and the rows'
-        parameters over. Until then no graph holds that kernel and no table is allocated."""
-        self.grammar = self._new_grammar()
-        self.sampler.grammar = self.grammar
-        self._swap_sampling_graphs()
-
-    def _enable_penalties(self) -> None:
-        """First penalised request (sampling already on): allocate the PenaltyState and, in graph
-        mode, replace every sampling graph by one whose step runs ``lsa_penalize`` in front of
-        ``lsa_sample``, carrying positions, tokens and the rows' parameters over. Until then no
-        graph holds the penalty kernel and no table is allocated."""
-        from ..runtime.sampling import PenaltyState
-        self.penalties = PenaltyState(self.eng, self.B * self.M)
-        self.sampler.penalties = self.penalties
+    def _enable_stage(self, name: str) -> None:
+        """First request that asks for the logit stage ``name`` (sampling already on): allocate its
+        state and, in graph mode, replace every sampling graph by one whose step holds its launch,
+        carrying positions, tokens and the rows' parameters over. Until then no graph holds that
+        kernel and no table is allocated."""
+        setattr(self, name, self._new_stage(name))
+        setattr(self.sampler, name, getattr(self, name))
         self._swap_sampling_graphs()
 
     def _enable_logprobs(self) -> None:
@@ -344,8 +323,7 @@ class PipelineServer:
         old, self.graphs = self.graphs, []
         for mb in range(self.M):
             g = SamplingDecodeGraph(self.eng, self.B, "full", slots=self._slots(mb), scratch=mb % self.S,
-                                    penalties=self.penalties, logprobs=self.logprobs_on,
-                                    constraints=self.constraints, grammar=self.grammar)
+                                    logprobs=self.logprobs_on, **self._stage_kw())
             g.pos.copy_(old[mb].pos)
             g.tokens.copy_(old[mb].tokens)
             for i, p in enumerate(getattr(old[mb], "params", ())):
@@ -367,7 +345,7 @@ class PipelineServer:
         sel = [i for i, r in enumerate(reqs) if r is not None and r.sampling is not None]
         if sel:
             pen = {}
-            if self.penalties is not None or self.constraints is not None or self.grammar is not None:
+            if ordered_stages(**self._stage_kw()):
                 pen = {"slots": [slots[i] for i in sel],
                        "tokens_in": None if tokens_in is None else [tokens_in[i] for i in sel]}
             want_lp = self.logprobs_on and any(reqs[i].sampling.logprobs is not None for i in sel)
@@ -421,23 +399,15 @@ class PipelineServer:
             self.eng = self._build_engine(start, end)
             self.start, self.end = start, end
             if self.sampling_on:
-                from ..runtime.sampling import PenaltyState, Sampler
-                if self.penalties is not None:  # drained: no request holds statistics
-                    self.penalties = None
-                    if self.gpu:
-                        torch.cuda.empty_cache()
-                    self.penalties = PenaltyState(self.eng, self.B * self.M)
-                if self.constraints is not None:  # drained: no slot holds an automaton; waiting requests
-                    self.constraints = None       # keep their references in the allocator
-                    if self.gpu:
-                        torch.cuda.empty_cache()
-                    self.constraints = self._new_constraints()
-                if self.grammar is not None:  # the same for the DFA arena
-                    self.grammar = None
-                    if self.gpu:
-                        torch.cuda.empty_cache()
-                    self.grammar = self._new_grammar()
-                self.sampler = Sampler(self.eng, self.penalties, self.constraints, self.grammar)
+                from ..runtime.sampling import Sampler
+                self.sampler = None
+                for name in STAGE_ORDER:  # drained: no slot holds statistics or an automaton; waiting
+                    if getattr(self, name) is not None:  # requests keep their references in the allocators
+                        setattr(self, name, None)
+                        if self.gpu:
+                            torch.cuda.empty_cache()
+                        setattr(self, name, self._new_stage(name))
+                self.sampler = Sampler(self.eng, **self._stage_kw())
             self._build_graphs()
             if self.gpu:
                 torch.cuda.synchronize(self.device)
@@ -577,22 +547,12 @@ class PipelineServer:
                 tok = eng.head(h, emit_rows).to(torch.int32)
                 if self.sampling_on:
                     em = [it for it in items if it[3]]
-                    if self.penalties is not None:  # a penalised request enters its slot
+                    for st in ordered_stages(**self._stage_kw()):  # the requests that ask for a stage enter their slots
                         for (s, _, _, _) in em:
                             r = self.by_slot.get(s)
-                            if r is not None and r.sampling is not None and r.sampling.penalized:
-                                self.penalties.admit(s, r.input_ids)
-                    if self.constraints is not None:  # a constrained request enters its slot
-                        for (s, _, _, _) in em:
-                            r = self.by_slot.get(s)
-                            if r is not None and r.constraint is not None:
-                                self.constraints.admit(s, r.sampling, len(r.input_ids), compiled=r.constraint,
-                                                       acquired=True)
-                    if self.grammar is not None:  # a request with a regex enters its slot
-                        for (s, _, _, _) in em:
-                            r = self.by_slot.get(s)
-                            if r is not None and r.grammar is not None:
-                                self.grammar.admit(s, r.sampling, acquired=True)
+                            if r is not None and r.sampling is not None and st.wants(r.sampling):
+                                held = {"constraints": r.constraint, "grammar": r.grammar}.get(st.name)
+                                st.enter(s, r.sampling, r.input_ids, reserved=held)  # held: reserved by submit
                     tok = self._sample_rows(h, emit_rows, [it[0] for it in em], [it[1] + it[2] for it in em], tok,
                                             mb=mb)
                     if self.graph_mode:  # the slot's parameters, before its first decode step
@@ -682,15 +642,13 @@ class PipelineServer:
                              f"{self.eng.max_seq}")
         constraint = None
         if sampling is not None and sampling.constrained:
-            from ..ops.constraints import ArenaAllocator
             from ..runtime.sampling import _check_full_head, compile_constraints
             _check_full_head(self.eng)
             constraint = compile_constraints(sampling, self.cfg.vocab_size, self.cfg.eos_ids)
             if constraint.automaton is not None:  # its rows of the arena, now: no room is an error now
+                arena = self._allocator("_arena", self.state_rows)
                 with self._lock:
-                    if self._arena is None:
-                        self._arena = ArenaAllocator(self.state_rows)
-                    self._arena.acquire(constraint.automaton)
+                    arena.acquire(constraint.automaton)
         grammar = None if sampling is None else sampling.grammar
         if grammar is not None:
             try:
@@ -714,7 +672,6 @@ class PipelineServer:
     def _reserve_grammar(self, dfa) -> None:
         """A request with a regex is submitted: check its DFA against the vocabulary's bytes and
         reserve its rows of the DFA arena (ValueError on either)."""
-        from ..ops.constraints import ArenaAllocator
         from ..runtime.sampling import _check_full_head, check_vocab_cache
         if self.vocab_bytes is None:
             raise ValueError("a regex needs the byte strings of the vocabulary: build the server with "
@@ -723,13 +680,12 @@ class PipelineServer:
             raise ValueError(f"vocab_bytes covers {self.vocab_bytes.V} tokens, the configuration has "
                              f"{self.cfg.vocab_size}")
         _check_full_head(self.eng)
+        garena = self._allocator("_garena", self.dfa_rows)
         with self._lock:
             if self._gcheck is None:
                 self._gcheck = check_vocab_cache(self.vocab_bytes, self.cfg.eos_ids)
-            if self._garena is None:
-                self._garena = ArenaAllocator(self.dfa_rows)
             self._gcheck(dfa)
-            self._garena.acquire(dfa)
+            garena.acquire(dfa)
 
     def submit_n(self, input_ids, n: int, max_new_tokens: int = 64, eos_ids=None, on_token=None,
                  reply_to: Optional[str] = None, sampling: Optional[SamplingParams] = None) -> List[int]:
@@ -879,14 +835,10 @@ class PipelineServer:
             r.on_token(r, tok)
         if tok in r.eos_ids or len(r.output_ids) >= r.max_new_tokens:
             r.state, r.t_done = DONE, now
-            if r.constraint is not None and self.constraints is not None:
-                self.constraints.release(r.slot)
-            if r.grammar is not None and self.grammar is not None:
-                fault = int(self.grammar.gfault[r.slot])
-                if fault:
-                    print(f"[WARN] request {r.rid}: grammar fault {fault} under regex {r.sampling.regex!r} (1: a token "
-                          "outside the pattern was fed, 2: a state allowed no token)", flush=True)
-                self.grammar.release(r.slot)
+            for st in ordered_stages(**self._stage_kw()):
+                warn = st.leave(r.slot, r.sampling) if r.sampling is not None and st.wants(r.sampling) else None
+                if warn:
+                    print(f"[WARN] request {r.rid}: {warn}", flush=True)
             mb = r.slot // self.B
             del self.by_slot[r.slot]
             self.cur_tok.pop(r.slot, None)
@@ -959,17 +911,14 @@ class PipelineServer:
             if not self.waiting or self._replan is not None:
                 break
             r = self.waiting.pop(0)
-            if r.sampling is not None and not self.sampling_on:
-                self._enable_sampling(penalties=r.sampling.penalized, logprobs=r.sampling.logprobs is not None,
-                                      constraints=r.constraint is not None, grammar=r.grammar is not None)
-            if r.grammar is not None and self.grammar is None:
-                self._enable_grammar()
-            if r.constraint is not None and self.constraints is None:
-                self._enable_constraints()
-            if r.sampling is not None and r.sampling.penalized and self.penalties is None:
-                self._enable_penalties()
-            if r.sampling is not None and r.sampling.logprobs is not None and not self.logprobs_on:
-                self._enable_logprobs()
+            if r.sampling is not None:
+                want = {c.name: c.wants(r.sampling) for c in STAGE_CLASSES}
+                if not self.sampling_on:
+                    self._enable_sampling(logprobs=r.sampling.logprobs is not None, **want)
+                for name in (n for n in STAGE_ORDER if want[n] and getattr(self, n) is None):
+                    self._enable_stage(name)
+                if r.sampling.logprobs is not None and not self.logprobs_on:
+                    self._enable_logprobs()
             r.slot, r.state, r.prefilled = s, PREFILLING, 0
             self.by_slot[s] = r
             if s in resets:

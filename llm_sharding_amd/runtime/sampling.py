@@ -11,23 +11,16 @@ path that exists only when a request asks for it.
   ``lsa_sample`` -> ``argmax_finalize`` instead of the fused argmax, with per-row parameters on
   the device (:meth:`SamplingDecodeGraph.set_params` between replays).
 * :class:`EagerSamplingDecode` - the same interface for CPU engines.
-* :class:`PenaltyState` - the per-slot token statistics of the repetition / presence / frequency
-  penalties (``ops.penalties``); it exists only once a request asks for a penalty, and a graph or
-  Sampler built without it runs exactly the code above.
-* :class:`ConstraintState` - the automaton arena and the per-slot tables of constrained decoding
-  (``ops.constraints``: logit bias, banned tokens, ``min_tokens``, min-p, token automata); it
-  exists only once a request asks for one of them, and a graph or Sampler built without it runs
-  exactly the code above. The order is penalise -> process -> sample -> logprobs.
-* :class:`GrammarState` - the byte-level DFA arena, the vocabulary's byte strings and the per-slot
-  states of regex-constrained decoding (``ops.grammar``, ``SamplingParams.regex``); it exists only
-  once a request carries a regex, and a graph or Sampler built without it runs exactly the code
-  above. With it the order is penalise -> grammar mask -> process -> sample -> logprobs: min-p sees
-  the masked row.
+* Logit stages (:mod:`.logit_stages`, re-exported here): :class:`PenaltyState`,
+  :class:`GrammarState` and :class:`ConstraintState`, optional per-slot state that edits the logits
+  between the lm_head and the draw. Each exists only once a request asks for it, and a Sampler or
+  graph built without one runs exactly the code above. Their order is defined once, in
+  ``logit_stages.STAGE_CLASSES``; the stages are followed by sample -> finalise -> logprobs.
 * Log-probabilities (``SamplingParams.logprobs``, ``ops.logprobs``): :meth:`Sampler.logprobs`,
   ``SamplingDecodeGraph(..., logprobs=True)`` (one ``lsa_logprobs`` launch behind
   ``argmax_finalize``; a graph built without it captures exactly the step above) and
   :func:`score_prompt`. The numbers describe the bf16 row ``lsa_sample`` reads: after the
-  penalties, before temperature and the top-k / top-p filters.
+  stages, before temperature and the top-k / top-p filters.
 
 A request's tokens depend only on its own logits, seed and positions (the noise is a pure
 function of seed, position and vocabulary index), not on the row, slot or batch it runs in.
@@ -40,15 +33,15 @@ import os
 from dataclasses import dataclass
 from typing import Any, Optional, Sequence
 
-import numpy as np
 import torch
 
 from ..ops import constraints as K
 from ..ops import grammar as G
 from ..ops import logprobs as LP
-from ..ops import penalties as P
 from ..ops import sampling as S
 from .engine import DecodeGraph, EagerDecode, StageEngine
+from .logit_stages import (STAGE_CLASSES, CompiledConstraint, ConstraintState, GrammarState,  # noqa: F401
+                           PenaltyState, _check_full_head, check_vocab_cache, compile_constraints, ordered_stages)
 
 
 @dataclass
@@ -268,352 +261,15 @@ def _compile_regex(pattern: str):
 GREEDY = SamplingParams(0.0, 0, 1.0, 0)
 
 
-def _check_full_head(eng: StageEngine) -> None:
-    if eng.lm_head is None:
-        raise RuntimeError("[ERROR] this stage has no lm_head")
-    if (eng.head_v0, eng.head_v1) != (0, eng.cfg.head_rows):
-        raise NotImplementedError("sampling needs the whole lm_head on one stage: this stage holds only vocabulary "
-                                  f"rows [{eng.head_v0}, {eng.head_v1}) of {eng.cfg.head_rows} (split head)")
-
-
-class PenaltyState:
-    """The token statistics of the penalties: ``uint16 [n_slots, head_rows]`` on the engine's
-    device (bit 15: the token occurs in the slot's prompt; bits 0..14: how often it has been
-    generated, saturating) - 32.8 MB at 512 slots x 32000. Built when the first penalised
-    request arrives, like the logits buffer. torch stores the table as int16 (same bits)."""
-
-    def __init__(self, eng: StageEngine, n_slots: int):
-        _check_full_head(eng)
-        self.eng, self.n_slots = eng, int(n_slots)
-        self.state = torch.zeros((self.n_slots, eng.cfg.head_rows), dtype=torch.int16, device=eng.device)
-
-    def admit(self, slot: int, prompt_ids) -> None:
-        """A penalised request enters ``slot``: zero its row, set the prompt bits."""
-        if not 0 <= slot < self.n_slots:
-            raise ValueError(f"slot {slot} outside the penalty table of {self.n_slots}")
-        ids = torch.as_tensor([int(t) for t in prompt_ids], dtype=torch.long, device=self.state.device)
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.eng.cfg.vocab_size):
-            raise ValueError("prompt token outside the vocabulary")
-        row = self.state[slot]
-        row.zero_()
-        row[ids] = -0x8000  # int16 pattern of bit 15
-
-    def counts(self, slot: int) -> torch.Tensor:
-        """Generated-token counts of ``slot`` (int32 [vocab_size], on the host)."""
-        return (self.state[slot, :self.eng.cfg.vocab_size].cpu().to(torch.int32) & P.COUNT_MAX)
-
-    def apply(self, logits: torch.Tensor, slots, tokens_in, params_list: Sequence["SamplingParams"]) -> torch.Tensor:
-        """Count ``tokens_in[i]`` (None: nothing) into ``slots[i]`` and penalise row i of bf16
-        ``logits`` [n, >= vocab_size] by ``params_list[i]``: ``lsa_penalize`` in place on the GPU,
-        the numpy reference on a CPU engine. Returns the penalised logits."""
-        n, V = logits.shape[0], self.eng.cfg.vocab_size
-        slots = [int(s) for s in slots]
-        if len(slots) != n or len(params_list) != n or (tokens_in is not None and len(tokens_in) != n):
-            raise ValueError(f"penalties: {n} rows, {len(slots)} slots, {len(params_list)} params")
-        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
-            raise ValueError(f"penalties: slots {slots} must be distinct and below {self.n_slots}")
-        rep, pres, freq = ([getattr(p, k) for p in params_list]
-                           for k in ("repetition_penalty", "presence_penalty", "frequency_penalty"))
-        if not self.eng.gpu:
-            out, st = P.penalize_reference(logits.to(torch.bfloat16), V, self.state, slots, tokens_in, rep, pres, freq)
-            self.state.copy_(torch.from_numpy(st.view("int16")))
-            return out
-        dev = self.eng.device
-        f32 = lambda x: torch.tensor(x, dtype=torch.float32, device=dev)  # noqa: E731
-        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
-        P.penalize(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin, self.state,
-                   f32(rep), f32(pres), f32(freq))
-        return logits
-
-
-@dataclass
-class CompiledConstraint:
-    """One request's constraint fields against a configuration: what :meth:`ConstraintState.admit`
-    writes into a slot."""
-    automaton: Optional[K.TokenAutomaton]
-    bias_tok: list
-    bias_val: list
-    min_tokens: int
-    minp_delta: float  # float32(T * ln(min_p)); -inf = off
-
-
-def compile_constraints(params: SamplingParams, vocab_size: int, eos_ids) -> CompiledConstraint:
-    """The checks of ``params``' constraint fields that need the vocabulary and the EOS ids
-    (ValueError), the automaton of ``allowed_token_ids`` / ``choices``, and ``minp_delta``."""
-    V, eos = int(vocab_size), [int(e) for e in eos_ids or ()]
-    if len(eos) > K.N_EOS:
-        raise ValueError(f"constraints: at most {K.N_EOS} EOS ids, the configuration has {len(eos)}")
-    entries = params.bias_entries()
-    if any(t >= V for t, _ in entries):
-        raise ValueError(f"logit_bias / banned_token_ids: token outside the vocabulary [0, {V})")
-    auto = params.automaton
-    if params.allowed_token_ids is not None:
-        auto = K.TokenAutomaton.from_allowed(params.allowed_token_ids, V)
-    elif params.choices is not None:
-        auto = K.TokenAutomaton.from_choices(params.choices, V, eos)
-    elif auto is not None and auto.vocab != V:
-        raise ValueError(f"automaton: a table over {auto.vocab} tokens for a vocabulary of {V}")
-    if auto is None:
-        gone = {t for t, b in entries if b == float("-inf")} | set(eos if params.min_tokens else ())
-        if len(gone) >= V:
-            raise ValueError("banned_token_ids and the EOS ids cover the whole vocabulary")
-    delta = float("-inf")
-    if params.min_p is not None and params.temperature > 0.0:
-        delta = float(np.float32(params.temperature * math.log(params.min_p)))
-    return CompiledConstraint(auto, [t for t, _ in entries], [b for _, b in entries], params.min_tokens, delta)
-
-
-class ConstraintState:
-    """The tables of constrained decoding (``ops.constraints``) on the engine's device: the
-    automaton arena ``int16 [state_rows, head_rows]`` (one row per automaton state - 256 rows are
-    16 MB at a vocabulary of 32000 and 66 MB at 128256), the per-slot rows ``astate / abase / bias_n
-    / bias_tok / bias_val / min_until / minp_delta / fault`` and the configuration's EOS ids. Built
-    when the first constrained request arrives. ``allocator`` (an :class:`ops.constraints.ArenaAllocator`
-    of ``state_rows`` rows, by default a new one) places automata in contiguous row ranges and
-    shares them by content digest; an automaton's rows are uploaded when its first request is
-    admitted."""
-
-    def __init__(self, eng: StageEngine, n_slots: int, state_rows: int = 256,
-                 allocator: Optional[K.ArenaAllocator] = None):
-        _check_full_head(eng)
-        self.eng, self.n_slots, self.state_rows = eng, int(n_slots), int(state_rows)
-        self.alloc = K.ArenaAllocator(self.state_rows) if allocator is None else allocator
-        if self.alloc.state_rows != self.state_rows or self.n_slots < 1:
-            raise ValueError("ConstraintState: the allocator must cover state_rows rows, and n_slots >= 1")
-        dev, n = eng.device, self.n_slots
-        self.arena = torch.full((self.state_rows, eng.cfg.head_rows), -1, dtype=torch.int16, device=dev)
-        self.astate = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        self.abase = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.bias_n = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.bias_tok = torch.zeros((n, K.BIAS_MAX), dtype=torch.int32, device=dev)
-        self.bias_val = torch.zeros((n, K.BIAS_MAX), dtype=torch.float32, device=dev)
-        self.min_until = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.minp_delta = torch.full((n,), float("-inf"), dtype=torch.float32, device=dev)
-        self.fault = torch.zeros(n, dtype=torch.int32, device=dev)
-        eos = [int(e) for e in eng.cfg.eos_ids][:K.N_EOS]
-        self.eos = torch.tensor(eos + [-1] * (K.N_EOS - len(eos)), dtype=torch.int32, device=dev)
-        self.resident: set = set()      # digests whose rows are in the arena
-        self.held: dict = {}            # slot -> digest of the automaton it holds
-
-    def compile(self, params: SamplingParams) -> CompiledConstraint:
-        return compile_constraints(params, self.eng.cfg.vocab_size, self.eng.cfg.eos_ids)
-
-    def admit(self, slot: int, params: Optional[SamplingParams], prompt_len: int,
-              compiled: Optional[CompiledConstraint] = None, acquired: bool = False) -> None:
-        """A request enters ``slot``: write its rows and point ``astate`` at its automaton's start
-        state. ``compiled`` / ``acquired``: the caller has compiled the fields, and already holds
-        the allocator's reference (the server does both when the request is submitted)."""
-        if not 0 <= slot < self.n_slots:
-            raise ValueError(f"slot {slot} outside the constraint tables of {self.n_slots}")
-        self.release(slot)
-        if params is None or not params.constrained:
-            return
-        c = self.compile(params) if compiled is None else compiled
-        base = -1
-        if c.automaton is not None:
-            d = c.automaton.digest
-            base = self.alloc.base(d) if acquired else self.alloc.acquire(c.automaton)
-            self.held[slot] = d
-            if d not in self.resident:
-                rows = torch.from_numpy(np.array(c.automaton.next)).to(self.arena.device)
-                self.arena[base:base + c.automaton.n_states, :c.automaton.vocab] = rows
-                if self.eng.gpu:  # streams other than this one may admit the same automaton next
-                    torch.cuda.current_stream(self.arena.device).synchronize()
-                self.resident.add(d)
-        n = len(c.bias_tok)
-        self.abase[slot] = max(base, 0)
-        self.astate[slot] = base
-        self.bias_n[slot] = n
-        if n:
-            dev = self.bias_tok.device
-            self.bias_tok[slot, :n] = torch.tensor(c.bias_tok, dtype=torch.int32, device=dev)
-            self.bias_val[slot, :n] = torch.tensor(c.bias_val, dtype=torch.float32, device=dev)
-        self.min_until[slot] = int(prompt_len) + c.min_tokens if c.min_tokens else 0
-        self.minp_delta[slot] = c.minp_delta
-        self.fault[slot] = 0
-
-    def release(self, slot: int) -> None:
-        """Clear ``slot``; the automaton it held loses one reference (``fault`` stays readable
-        until the next :meth:`admit`)."""
-        d = self.held.pop(slot, None)
-        if d is not None and self.alloc.release(d):
-            self.resident.discard(d)
-        self.astate[slot] = -1
-        self.bias_n[slot] = 0
-        self.min_until[slot] = 0
-        self.minp_delta[slot] = float("-inf")
-
-    def apply(self, logits: torch.Tensor, slots, tokens_in, positions) -> torch.Tensor:
-        """Advance ``slots[i]`` by ``tokens_in[i]`` (None: nothing) and process row i of bf16
-        ``logits`` [n, >= vocab_size]; ``positions[i]`` is the position the sampled token will
-        occupy. ``lsa_logit_process`` in place on the GPU, the numpy reference on a CPU engine.
-        Returns the processed logits."""
-        n, V = logits.shape[0], self.eng.cfg.vocab_size
-        slots = [int(s) for s in slots]
-        positions = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
-        if len(slots) != n or len(positions) != n or (tokens_in is not None and len(tokens_in) != n):
-            raise ValueError(f"constraints: {n} rows, {len(slots)} slots, {len(positions)} positions")
-        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
-            raise ValueError(f"constraints: slots {slots} must be distinct and below {self.n_slots}")
-        if not self.eng.gpu:
-            out, ast, flt = K.logit_process_reference(logits.to(torch.bfloat16), V, self, slots, tokens_in, positions)
-            self.astate.copy_(torch.from_numpy(ast))
-            self.fault.copy_(torch.from_numpy(flt))
-            return out
-        dev = self.eng.device
-        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
-        K.logit_process(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin,
-                        torch.tensor(positions, dtype=torch.int32, device=dev), self)
-        return logits
-
-
-class GrammarState:
-    """The tables of regex-constrained decoding (``ops.grammar``) on the engine's device: the DFA
-    arena ``int16 [dfa_rows, 256]`` with its ``accept`` bytes (513 B per state whatever the
-    vocabulary - 2 MB at the default 4096 rows, where the dense arena of :class:`ConstraintState`
-    takes 64 KB per state at a vocabulary of 32000), the vocabulary's byte strings (``offsets``,
-    ``data``), the per-slot rows ``gstate / gbase / gfault`` (12 B per slot) and the configuration's
-    EOS ids. Built when the first request with a regex arrives. ``allocator`` (an
-    :class:`ops.constraints.ArenaAllocator` of ``dfa_rows`` rows, by default a new one) places DFAs
-    in contiguous row ranges and shares them by content digest; a DFA's rows are uploaded when its
-    first request is admitted."""
-
-    def __init__(self, eng: StageEngine, n_slots: int, vocab: "G.VocabBytes", dfa_rows: int = 4096,
-                 allocator: Optional[K.ArenaAllocator] = None):
-        _check_full_head(eng)
-        self.eng, self.n_slots, self.dfa_rows, self.vocab = eng, int(n_slots), int(dfa_rows), vocab
-        if not isinstance(vocab, G.VocabBytes) or vocab.V != eng.cfg.vocab_size:
-            raise ValueError(f"GrammarState: a VocabBytes over the configuration's {eng.cfg.vocab_size} tokens, got "
-                             f"{getattr(vocab, 'V', None)}")
-        self.alloc = K.ArenaAllocator(self.dfa_rows) if allocator is None else allocator
-        if self.alloc.state_rows != self.dfa_rows or self.n_slots < 1:
-            raise ValueError("GrammarState: the allocator must cover dfa_rows rows, and n_slots >= 1")
-        dev, n = eng.device, self.n_slots
-        self.arena = torch.full((self.dfa_rows, 256), -1, dtype=torch.int16, device=dev)
-        self.accept = torch.zeros(self.dfa_rows, dtype=torch.uint8, device=dev)
-        self.offsets = torch.from_numpy(np.array(vocab.offsets)).to(dev)
-        self.data = torch.from_numpy(np.array(vocab.data)).to(dev)
-        self.gstate = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        self.gbase = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.gfault = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.eos_ids = [int(e) for e in eng.cfg.eos_ids][:K.N_EOS]
-        self.eos = torch.tensor(self.eos_ids + [-1] * (K.N_EOS - len(self.eos_ids)), dtype=torch.int32, device=dev)
-        self.resident: set = set()      # digests whose rows are in the arena
-        self.held: dict = {}            # slot -> digest of the DFA it holds
-        self.checked = check_vocab_cache(vocab, self.eos_ids)
-
-    def check(self, dfa: "G.ByteDFA") -> None:
-        """ValueError unless every state of ``dfa`` allows at least one token of this vocabulary."""
-        self.checked(dfa)
-
-    def admit(self, slot: int, params: Optional[SamplingParams], acquired: bool = False) -> None:
-        """A request enters ``slot``: point ``gstate`` at its DFA's start state (uploading the DFA's
-        rows when it is new). ``acquired``: the caller already holds the allocator's reference and
-        has run :meth:`check` (the server does both when the request is submitted)."""
-        if not 0 <= slot < self.n_slots:
-            raise ValueError(f"slot {slot} outside the grammar tables of {self.n_slots}")
-        self.release(slot)
-        dfa = None if params is None else params.grammar
-        if dfa is None:
-            return
-        if not acquired:
-            self.check(dfa)
-        d = dfa.digest
-        base = self.alloc.base(d) if acquired else self.alloc.acquire(dfa)
-        self.held[slot] = d
-        if d not in self.resident:
-            S = dfa.n_states
-            flags = dfa.accept.astype(np.uint8) * G.ACCEPT
-            flags[S - 1] |= G.LAST
-            self.arena[base:base + S] = torch.from_numpy(np.array(dfa.next)).to(self.arena.device)
-            self.accept[base:base + S] = torch.from_numpy(flags).to(self.arena.device)
-            if self.eng.gpu:  # streams other than this one may admit the same DFA next
-                torch.cuda.current_stream(self.arena.device).synchronize()
-            self.resident.add(d)
-        self.gbase[slot] = base
-        self.gstate[slot] = base
-        self.gfault[slot] = 0
-
-    def release(self, slot: int) -> None:
-        """Clear ``slot``; the DFA it held loses one reference (``gfault`` stays readable until the
-        next :meth:`admit`)."""
-        d = self.held.pop(slot, None)
-        if d is not None and self.alloc.release(d):
-            self.resident.discard(d)
-        self.gstate[slot] = -1
-
-    def apply(self, logits: torch.Tensor, slots, tokens_in) -> torch.Tensor:
-        """Advance ``slots[i]`` by the bytes of ``tokens_in[i]`` (None: nothing) and mask row i of
-        bf16 ``logits`` [n, >= vocab_size]: ``lsa_grammar_mask`` in place on the GPU, the numpy
-        reference on a CPU engine. Returns the masked logits."""
-        n, V = logits.shape[0], self.eng.cfg.vocab_size
-        slots = [int(s) for s in slots]
-        if len(slots) != n or (tokens_in is not None and len(tokens_in) != n):
-            raise ValueError(f"grammar: {n} rows, {len(slots)} slots")
-        if len(set(slots)) != n or any(not 0 <= s < self.n_slots for s in slots):
-            raise ValueError(f"grammar: slots {slots} must be distinct and below {self.n_slots}")
-        if not self.eng.gpu:
-            out, gst, flt = G.grammar_mask_reference(logits.to(torch.bfloat16), V, self, slots, tokens_in)
-            self.gstate.copy_(torch.from_numpy(gst))
-            self.gfault.copy_(torch.from_numpy(flt))
-            return out
-        dev = self.eng.device
-        tin = None if tokens_in is None else torch.tensor([int(t) for t in tokens_in], dtype=torch.int32, device=dev)
-        G.grammar_mask(logits, V, n, torch.tensor(slots, dtype=torch.int32, device=dev), tin, self)
-        return logits
-
-
-def check_vocab_cache(vocab: "G.VocabBytes", eos_ids):
-    """A function ``check(dfa)`` that raises ValueError unless every state of ``dfa`` allows at least
-    one token of ``vocab`` - so a row can never lose every column. First the cheap sufficient test
-    (the state accepts and an EOS id exists, or a live byte of it exists as a one-byte token), then,
-    only for the states that fail it, the exact vectorised walk. Results are kept per digest."""
-    eos = [int(e) for e in eos_ids if 0 <= int(e) < vocab.V]
-    ln = np.diff(vocab.offsets)
-    one = ln == 1
-    one[eos] = False                      # an EOS id's own bytes are ignored
-    single = np.zeros(256, dtype=bool)
-    single[vocab.data[vocab.offsets[:-1][one]]] = True
-    done: dict = {}
-
-    def check(dfa) -> None:
-        bad = done.get(dfa.digest)
-        if bad is None:
-            ok = ((np.asarray(dfa.next) >= 0) & single[None, :]).any(axis=1)
-            if eos:
-                ok |= np.asarray(dfa.accept)
-            bad = -1
-            rest = np.nonzero(~ok)[0]
-            for c0 in range(0, rest.size, 64):  # the exact walk, 64 states at a time
-                alive = dfa.step_tokens(vocab, rest[c0:c0 + 64]) >= 0
-                alive[:, eos] = False
-                stuck = np.nonzero(~alive.any(axis=1))[0]
-                if stuck.size:
-                    bad = int(rest[c0 + stuck[0]])
-                    break
-            if len(done) >= 1024:
-                done.pop(next(iter(done)))
-            done[dfa.digest] = bad
-        if bad >= 0:
-            raise ValueError(f"regex {dfa.pattern!r}: state {bad} of its automaton allows no token of this "
-                             "vocabulary (no token's bytes continue a match there)")
-
-    return check
-
-
 class Sampler:
-    """Logits and sampled tokens of a stage that holds the whole lm_head. ``penalties``: the
-    stage's :class:`PenaltyState`, applied by :meth:`sample` to the rows given ``slots``;
-    ``grammar``: its :class:`GrammarState`, applied behind the penalties; ``constraints``: its
-    :class:`ConstraintState`, applied behind both."""
+    """Logits and sampled tokens of a stage that holds the whole lm_head. ``penalties``,
+    ``constraints``, ``grammar``: its logit stages (:mod:`.logit_stages`), applied by :meth:`sample`
+    to the rows given ``slots``, in the stages' one order."""
 
     def __init__(self, eng: StageEngine, penalties: Optional[PenaltyState] = None,
                  constraints: Optional[ConstraintState] = None, grammar: Optional[GrammarState] = None):
         _check_full_head(eng)
-        self.eng = eng
-        self.penalties = penalties
-        self.constraints = constraints
-        self.grammar = grammar
+        self.eng, self.penalties, self.constraints, self.grammar = eng, penalties, constraints, grammar
 
     # ------------------------------------------------------------------ logits
     def logits(self, h: torch.Tensor, rows_idx=None) -> torch.Tensor:
@@ -732,30 +388,19 @@ class Sampler:
     def sample(self, h: torch.Tensor, rows_idx, params_list: Sequence[SamplingParams], positions,
                slots=None, tokens_in=None, return_logprobs: bool = False):
         """Sampled tokens (int64 [n]) of the selected rows of the final hidden ``h``: the first
-        token after a prefill uses ``positions[i]`` = the prompt length. ``slots`` (with a
-        :class:`PenaltyState`): row i belongs to sequence slot ``slots[i]`` and is penalised by
-        its parameters first; ``tokens_in[i]`` is the token the row's step was fed (counted as
-        generated) - None for the first token after a prefill, which only sees the prompt. With a
-        :class:`ConstraintState` the rows of constrained requests are then processed
-        (``ops.constraints``: the automaton advances by ``tokens_in[i]``), in the order penalise ->
-        process -> sample -> logprobs. With a :class:`GrammarState` the rows whose slots hold a regex
-        are masked between the two (``ops.grammar``).
+        token after a prefill uses ``positions[i]`` = the prompt length. ``slots`` (with a logit
+        stage): row i belongs to sequence slot ``slots[i]`` and is edited first by every stage one of
+        the rows' parameters asks for (:mod:`.logit_stages`, in their order); ``tokens_in[i]`` is the
+        token the row's step was fed - None for the first token after a prefill, which only sees the prompt.
         ``return_logprobs``: returns ``(tokens, Logprobs)`` - the log-probabilities of the sampled
-        tokens under the (penalised) logits, for the rows whose parameters ask for them."""
+        tokens under the edited logits, for the rows whose parameters ask for them."""
         logits = self.logits(h, rows_idx)
-        if any(p.penalized for p in params_list):
-            if self.penalties is None or slots is None:
-                raise RuntimeError("a penalised request needs a PenaltyState (Sampler(eng, penalties=...)) and slots=")
-            logits = self.penalties.apply(logits, slots, tokens_in, params_list)
-        if any(p.grammar is not None for p in params_list):
-            if self.grammar is None or slots is None:
-                raise RuntimeError("a request with a regex needs a GrammarState (Sampler(eng, grammar=...)) and slots=")
-            logits = self.grammar.apply(logits, slots, tokens_in)
-        if any(p.constrained for p in params_list):
-            if self.constraints is None or slots is None:
-                raise RuntimeError("a constrained request needs a ConstraintState (Sampler(eng, constraints=...)) and "
-                                   "slots=")
-            logits = self.constraints.apply(logits, slots, tokens_in, positions)
+        for cls in STAGE_CLASSES:
+            if any(cls.wants(p) for p in params_list):
+                stage = getattr(self, cls.name)
+                if stage is None or slots is None:
+                    raise RuntimeError(cls.needs())
+                logits = stage.apply(logits, slots, tokens_in, params_list=params_list, positions=positions)
         tok = self.sample_logits(logits, params_list, positions)
         if not return_logprobs:
             return tok
@@ -779,32 +424,20 @@ class SamplingDecodeGraph(DecodeGraph):
     parameters between replays. The row's Philox counter is its device position + 1 - the
     position the sampled token will occupy - so no host work happens per token.
 
-    With ``penalties`` (a :class:`PenaltyState` that covers this graph's slots) the step is logits
-    -> ``lsa_penalize`` -> ``lsa_sample``: the kernel counts the step's input tokens
-    (``self.tokens``) into the rows' slots and edits the logits by the per-row ``rep / pres / freq``
-    device arrays; rows whose penalties are off are skipped. Without it the captured step is
-    exactly the one above. ``debug_raw`` keeps a captured copy of the unpenalised logits in
-    ``raw_logits``.
+    With ``penalties``, ``grammar`` or ``constraints`` (logit stages that cover this graph's slots,
+    :mod:`.logit_stages`) the step holds one launch per stage between the logits and ``lsa_sample``,
+    in the stages' order, on the step's input tokens (``self.tokens``) and the per-slot device
+    tables; rows whose slots hold nothing for a stage are skipped by its kernel, and the
+    log-probabilities describe the edited row. ``debug_raw`` keeps a captured copy of the unedited
+    logits in ``raw_logits``.
 
     With ``logprobs=True`` the step ends in one more launch, ``lsa_logprobs`` on the same logits
     with the freshly written ``self.tokens`` as targets: the per-row ``n_top`` (-1 = the row is
     skipped, written by :meth:`set_params`) and the outputs ``lp`` (:class:`ops.logprobs.Logprobs`)
     live on the device; with a token history, ``lp_history`` keeps ``tok_lp`` of the same steps
-    (NaN where a row was skipped). Without it the captured step is exactly the one above.
+    (NaN where a row was skipped).
 
-    With ``constraints`` (a :class:`ConstraintState` that covers this graph's slots) one
-    ``lsa_logit_process`` launch sits between ``lsa_penalize`` and ``lsa_sample``: it advances the
-    rows' automaton states by the step's input tokens and applies bias, EOS mask, automaton mask
-    and min-p from the per-slot device tables (written by :meth:`ConstraintState.admit`); rows
-    whose slots hold no constraint are skipped. The log-probabilities then describe the processed
-    row. Without it the captured step is exactly the one above.
-
-    With ``grammar`` (a :class:`GrammarState` that covers this graph's slots) one
-    ``lsa_grammar_mask`` launch sits between ``lsa_penalize`` and ``lsa_logit_process``: it advances
-    the rows' DFA states by the bytes of the step's input tokens and masks every token whose bytes
-    die in the automaton; rows whose slots hold no regex are skipped. Without it the captured step
-    is exactly the one above.
-
+    Without any one of them the captured step is exactly what it would be if that one did not exist.
     The logits buffer (``rows x head_rows`` bf16, 32 MB at 512 x 32000) is allocated only here."""
 
     def __init__(self, eng: StageEngine, rows: int, mode: str, slots: Optional[list] = None,
@@ -820,22 +453,13 @@ class SamplingDecodeGraph(DecodeGraph):
         for k, v in device_params(self.params, dev).items():
             setattr(self, k, v)
         self.logits = torch.zeros((rows, eng.cfg.head_rows), dtype=torch.bfloat16, device=dev)
-        self.penalties = penalties
         self.raw_logits = torch.zeros_like(self.logits) if debug_raw else None
-        if penalties is not None:
-            if penalties.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= penalties.n_slots:
-                raise ValueError("penalties: a PenaltyState of this engine with a distinct row per graph slot")
-            self.rep = torch.ones(rows, dtype=torch.float32, device=dev)
-            self.pres = torch.zeros(rows, dtype=torch.float32, device=dev)
-            self.freq = torch.zeros(rows, dtype=torch.float32, device=dev)
-        self.constraints = constraints
-        if constraints is not None:
-            if constraints.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= constraints.n_slots:
-                raise ValueError("constraints: a ConstraintState of this engine with a distinct row per graph slot")
-        self.grammar = grammar
-        if grammar is not None:
-            if grammar.eng is not eng or len(set(self.slots)) != rows or max(self.slots) >= grammar.n_slots:
-                raise ValueError("grammar: a GrammarState of this engine with a distinct row per graph slot")
+        self.penalties, self.constraints, self.grammar = penalties, constraints, grammar
+        self.stages = ordered_stages(penalties, constraints, grammar)
+        self.stage_rows = {}  # stage name -> its per-row device arrays
+        for st in self.stages:
+            st.check_covers(eng, self.slots, rows)
+            self.stage_rows[st.name] = st.device_rows(self.params, dev)
         self.lp = self.n_top = self.lp_history = None
         if logprobs:
             self.n_top = torch.full((rows,), -1, dtype=torch.int32, device=dev)
@@ -845,46 +469,25 @@ class SamplingDecodeGraph(DecodeGraph):
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
         """Small host-to-device copies on the current stream (like ``set_positions``)."""
-        p = GREEDY if params is None else params
-        if p.penalized and self.penalties is None:
-            raise RuntimeError("a penalised request needs SamplingDecodeGraph(..., penalties=PenaltyState)")
-        if p.logprobs is not None and self.lp is None:
-            raise RuntimeError("a request with logprobs needs SamplingDecodeGraph(..., logprobs=True)")
-        if p.constrained and self.constraints is None:
-            raise RuntimeError("a constrained request needs SamplingDecodeGraph(..., constraints=ConstraintState)")
-        if p.grammar is not None and self.grammar is None:
-            raise RuntimeError("a request with a regex needs SamplingDecodeGraph(..., grammar=GrammarState)")
+        p = _checked_params(self, params)
         self.params[row] = p
         self.temperature[row] = p.temperature
         self.top_k[row] = p.top_k
         self.top_p[row] = p.top_p
         self.seed[row] = S.seed_to_i64(p.seed)
-        if self.penalties is not None:
-            self.rep[row] = p.repetition_penalty
-            self.pres[row] = p.presence_penalty
-            self.freq[row] = p.frequency_penalty
+        for st in self.stages:
+            st.write_row(self.stage_rows[st.name], row, p)
         if self.lp is not None:
             self.n_top[row] = p.n_top
 
     def capture(self, warmup: bool = True) -> "SamplingDecodeGraph":
-        """The warm-up run counts tokens into the penalty state and advances the automaton and
-        grammar states: the graph's rows are restored."""
-        cs, gs = self.constraints, self.grammar
+        """The warm-up run advances the stages' per-slot state (token counts, automaton and DFA
+        states): the graph's rows are restored."""
         idx = self.slot.long()
-        kept = None if cs is None else (cs.astate.index_select(0, idx), cs.fault.index_select(0, idx))
-        gkept = None if gs is None else (gs.gstate.index_select(0, idx), gs.gfault.index_select(0, idx))
-        if self.penalties is None:
-            super().capture(warmup)
-        else:
-            saved = self.penalties.state.index_select(0, idx)
-            super().capture(warmup)
-            self.penalties.state.index_copy_(0, idx, saved)
-        if kept is not None:
-            cs.astate.index_copy_(0, idx, kept[0])
-            cs.fault.index_copy_(0, idx, kept[1])
-        if gkept is not None:
-            gs.gstate.index_copy_(0, idx, gkept[0])
-            gs.gfault.index_copy_(0, idx, gkept[1])
+        saved = [st.snapshot(idx) for st in self.stages]
+        super().capture(warmup)
+        for st, kept in zip(self.stages, saved):
+            st.restore(idx, kept)
         if self.lp_history is not None:
             self.lp_history.fill_(float("nan"))
         return self
@@ -900,14 +503,8 @@ class SamplingDecodeGraph(DecodeGraph):
         self.sampler.logits_into(h, rows, self.logits)
         if self.raw_logits is not None:
             self.raw_logits.copy_(self.logits)
-        if self.penalties is not None:
-            P.penalize(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.penalties.state,
-                       self.rep, self.pres, self.freq)
-        if self.grammar is not None:
-            G.grammar_mask(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.grammar)
-        if self.constraints is not None:
-            K.logit_process(self.logits, eng.cfg.vocab_size, rows, self.slot, self.tokens, self.pos, self.constraints,
-                            ctr_add=1)
+        for st in self.stages:
+            st.launch(self)
         S.sample(self.logits, eng.cfg.vocab_size, rows, self.temperature, self.top_k, self.top_p, self.seed, self.pos,
                  self.keys, ctr_add=1)
         hip.argmax_finalize(self.keys, rows, self.tokens, self.pos, 1, self.history,
@@ -915,6 +512,18 @@ class SamplingDecodeGraph(DecodeGraph):
         if self.lp is not None:
             LP.logprobs(self.logits, eng.cfg.vocab_size, rows, self.n_top, self.tokens, self.lp,
                         lp_history=self.lp_history, step_ctr=self.step_ctr if self.lp_history is not None else None)
+
+
+def _checked_params(graph, params: Optional[SamplingParams]) -> SamplingParams:
+    """``params`` (None: greedy), or RuntimeError: they need a stage or logprobs ``graph`` lacks."""
+    p = GREEDY if params is None else params
+    owner = type(graph).__name__
+    for cls in STAGE_CLASSES:
+        if cls.wants(p) and getattr(graph, cls.name) is None:
+            raise RuntimeError(cls.needs(owner))
+    if p.logprobs is not None and graph.lp is None:
+        raise RuntimeError(f"a request with logprobs needs {owner}(..., logprobs=True)")
+    return p
 
 
 class EagerSamplingDecode(EagerDecode):
@@ -927,9 +536,8 @@ class EagerSamplingDecode(EagerDecode):
             raise ValueError("EagerSamplingDecode runs the head: mode 'full' or 'last'")
         super().__init__(eng, rows, mode, slots=slots, history_len=history_len)
         self.sampler = Sampler(eng, penalties, constraints, grammar)
-        self.penalties = penalties
-        self.constraints = constraints
-        self.grammar = grammar
+        self.penalties, self.constraints, self.grammar = penalties, constraints, grammar
+        self.stages = ordered_stages(penalties, constraints, grammar)
         self.params = [GREEDY] * rows
         self.lp = self.lp_history = None
         if logprobs:
@@ -938,14 +546,7 @@ class EagerSamplingDecode(EagerDecode):
                 self.lp_history = torch.full(self.history.shape, float("nan"), dtype=torch.float32)
 
     def set_params(self, row: int, params: Optional[SamplingParams]) -> None:
-        p = GREEDY if params is None else params
-        if p.logprobs is not None and self.lp is None:
-            raise RuntimeError("a request with logprobs needs EagerSamplingDecode(..., logprobs=True)")
-        if p.constrained and self.constraints is None:
-            raise RuntimeError("a constrained request needs EagerSamplingDecode(..., constraints=ConstraintState)")
-        if p.grammar is not None and self.grammar is None:
-            raise RuntimeError("a request with a regex needs EagerSamplingDecode(..., grammar=GrammarState)")
-        self.params[row] = p
+        self.params[row] = _checked_params(self, params)
 
     def _body(self) -> None:
         eng = self.eng
@@ -953,9 +554,7 @@ class EagerSamplingDecode(EagerDecode):
         slot, pos = eng.prefill_rows(self.slots, [1] * self.rows)
         h = eng.forward(h, slot, pos)
         eng.advance(self.slots, [1] * self.rows)
-        pen = {}
-        if self.penalties is not None or self.constraints is not None or self.grammar is not None:
-            pen = {"slots": self.slots, "tokens_in": self.tokens.tolist()}
+        pen = {"slots": self.slots, "tokens_in": self.tokens.tolist()} if self.stages else {}
         tok = self.sampler.sample(h, None, self.params, [p + 1 for p in pos], return_logprobs=self.lp is not None,
                                   **pen)
         if self.lp is not None:
