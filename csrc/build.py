@@ -58,10 +58,12 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     # csrc/sampling/: the sampling kernels, outside the greedy path's recorded numerics inputs
     # csrc/cache/: KV-cache management (fork), outside them too
     # csrc/spec/: speculative decoding's draft / accept kernels, outside them too
+    # csrc/quant/: the int4 weight format's decode GEMV, which the bf16 greedy path never launches
     kernel_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) +
                          glob.glob(os.path.join(CSRC, "sampling", "*.hip")) +
                          glob.glob(os.path.join(CSRC, "cache", "*.hip")) +
-                         glob.glob(os.path.join(CSRC, "spec", "*.hip")))
+                         glob.glob(os.path.join(CSRC, "spec", "*.hip")) +
+                         glob.glob(os.path.join(CSRC, "quant", "*.hip")))
     comm_srcs = sorted(glob.glob(os.path.join(CSRC, "comm", "*.cpp")))
     # -fno-slp-vectorize: no packed-FP32 VALU formed from scalar code (the remaining packed FP32
     # comes from explicit vector code). Packed FP32 beside MFMAs is an anti-lever

@@ -44,7 +44,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from llm_sharding_amd.config import LlamaConfig, get_preset  # noqa: E402
 from llm_sharding_amd.models.tokenizer import SyntheticByteTokenizer, load_tokenizer  # noqa: E402
-from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, ShardFolderSource, StageEngine  # noqa: E402
+from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, ShardFolderSource  # noqa: E402
+from llm_sharding_amd.runtime.engine_int4 import make_stage_engine  # noqa: E402
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -54,6 +55,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prompt", default="Write a poem about the blue sky.")
     ap.add_argument("--max-new-tokens", type=int, default=128)
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
+                    help="projection weights on the GPU: bf16, fp8 (OCP e4m3, per-row scales, fp8 lm_head) or int4 "
+                         "(symmetric group-128, bf16 lm_head); ignored on the CPU")
     ap.add_argument("--hf-compare", default="", help="HF checkpoint dir: also run transformers' greedy generate "
                                                      "(the reference inference.py's path, fp32 CPU) and compare tokens")
     ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy decode")
@@ -176,8 +180,8 @@ def main(argv=None):
         src, tok = RandomSource(cfg), SyntheticByteTokenizer(cfg.vocab_size)
     dt = torch.bfloat16 if a.device.startswith("cuda") else torch.float32
     t0 = time.perf_counter()
-    eng = StageEngine(cfg, 0, cfg.num_hidden_layers, a.device, dt, has_embed=True, has_head=True, source=src,
-                      max_seq=min(cfg.max_position_embeddings, 4096))
+    eng = make_stage_engine(cfg, 0, cfg.num_hidden_layers, a.device, dt, has_embed=True, has_head=True, source=src,
+                            max_seq=min(cfg.max_position_embeddings, 4096), weight_dtype=a.weight_dtype)
     ids = tok(a.prompt, return_tensors="pt")["input_ids"][0]
     if a.choice:
         sp = sampling_from_args(a, [tok.encode(c, add_special_tokens=False) for c in a.choice])

@@ -29,6 +29,7 @@ import torch
 
 from ..config import get_preset
 from ..runtime.engine import DecodeGraph, EagerDecode, RandomSource, StageEngine
+from ..runtime.engine_int4 import make_stage_engine
 from ..utils import tracing
 from .scheduler import plan_stages, scratch_bytes, stage_memory
 
@@ -266,11 +267,11 @@ class PipelineStage:
                 raise ValueError("PipelineStage: the shared engine does not match this stage")
             self.eng = engine
         else:
-            self.eng = StageEngine(cfg, start, end, device, self.dtype, has_embed=self.first,
-                                   has_head=self.last or (self.split and self.first), source=source,
-                                   max_slots=batch * microbatches, max_seq=max_seq,
-                                   max_prefill_rows=max(max_prefill_rows, batch), head_cols=head_cols,
-                                   weight_dtype=weight_dtype)
+            self.eng = make_stage_engine(cfg, start, end, device, self.dtype, has_embed=self.first,
+                                         has_head=self.last or (self.split and self.first), source=source,
+                                         max_slots=batch * microbatches, max_seq=max_seq,
+                                         max_prefill_rows=max(max_prefill_rows, batch), head_cols=head_cols,
+                                         weight_dtype=weight_dtype)
         H = cfg.hidden_size
         self.h_out = [torch.zeros((batch, H), dtype=self.dtype, device=self.device) for _ in range(microbatches)]
         self.tok_out = [torch.zeros(batch, dtype=torch.int32, device=self.device) for _ in range(microbatches)]
@@ -851,7 +852,8 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     v1 = (V // 2) // 128 * 128 if pp > 1 else V
     head_rows = (v1 if st.has_head else 0) + (V - v1 if (pp > 1 and st.has_embed) else 0)
     mem_pred = stage_memory(cfg, st.n_layers, slots=batch * M, max_seq=max_seq, prefill_rows=batch * prompt_len,
-                            has_embed=st.has_embed, head_rows=head_rows, scratch_sets=S_sets, io_rows=batch * M)
+                            has_embed=st.has_embed, head_rows=head_rows, scratch_sets=S_sets, io_rows=batch * M,
+                            weight_dtype=weight_dtype)
     if need > max_seq:
         raise ValueError(f"prompt+warmup+steps ({need}) exceeds max_seq {max_seq}")
     if verbose and rank == 0:

@@ -201,19 +201,29 @@ def scratch_bytes(cfg: LlamaConfig, rows: int, sets: int = 1, max_seq: int = 409
 
 def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, prefill_rows: int,
                  has_embed: bool = False, head_rows: int = 0, scratch_sets: int = 1,
-                 io_rows: int = 0, elem_bytes: int = 2) -> dict:
+                 io_rows: int = 0, elem_bytes: int = 2, weight_dtype: str = "bf16") -> dict:
     """Device bytes of one pipeline stage as the engine allocates them (weights, static KV cache,
     scratch) - the memory table the bench's stage sizing relies on (profiles/memory_table.md).
     ``head_rows``: lm_head rows held on this stage (split head: a part of the vocabulary);
-    ``io_rows``: per-micro-batch hidden/token hand-off buffers (PipelineStage.h_out/tok_out)."""
+    ``io_rows``: per-micro-batch hidden/token hand-off buffers (PipelineStage.h_out/tok_out).
+    ``weight_dtype="int4"``: the four projections of a layer at 4.25 bits per weight (nibbles +
+    fp32 group-128 scales; embedding, lm_head and norms stay ``elem_bytes``), plus one
+    projection-sized bf16 dequantisation buffer per scratch set. Any other value ("fp8" too, which
+    this table never modelled) counts the weights at ``elem_bytes``."""
     H = cfg.hidden_size
     w = n_layers * cfg.layer_bytes(elem_bytes)
+    w_scratch = 0
+    if weight_dtype == "int4":
+        from ..ops import int4
+        shapes = [(cfg.qkv_size, H), (H, cfg.q_size), (cfg.mlp_in_size, H), (H, cfg.intermediate_size)]
+        w += n_layers * sum(int4.int4_bytes(n, k) - n * k * elem_bytes for n, k in shapes)
+        w_scratch = scratch_sets * 2 * max(n * k for n, k in shapes)
     if has_embed:
         w += cfg.vocab_size * H * elem_bytes
     if head_rows:
         w += head_rows * H * elem_bytes + H * elem_bytes          # lm_head part + final norm
     kv = n_layers * cfg.kv_bytes_per_token_per_layer(elem_bytes) * slots * max_seq
-    scratch = scratch_bytes(cfg, prefill_rows, scratch_sets, max_seq, head_rows)
+    scratch = scratch_bytes(cfg, prefill_rows, scratch_sets, max_seq, head_rows) + w_scratch
     io = io_rows * (H * elem_bytes + 4 + 8)
     return {"weights": float(w), "kv": float(kv), "scratch": float(scratch), "io": float(io),
             "total": float(w + kv + scratch + io)}

@@ -27,7 +27,10 @@ it to bf16; norms and the embedding stay bf16 (suffixes as in the reference:
   ``<name>_scale`` fp32 [N] (w ~= q * scale, |q| <= 127);
 * ``torch.int4`` - symmetric group-wise int4 (``INT4_GROUP`` = 128 input channels per
   scale), two values per byte, even k in the low nibble: ``<name>`` uint8 [N, K/2] +
-  ``<name>_scale`` fp32 [N, K/128] (|q| <= 7).
+  ``<name>_scale`` fp32 [N, K/128] (|q| <= 7). ``make_stage_engine(weight_dtype="int4")`` decodes on
+  this format natively (csrc/quant/gemv_int4.hip), but re-quantises each fused projection after folding
+  its RMSNorm weight in (ops/int4.py ``quantize_int4_groups``, this file's arithmetic), so
+  the shard's own nibbles are dequantised at load like the other formats.
 """
 from __future__ import annotations
 

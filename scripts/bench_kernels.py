@@ -14,7 +14,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from llm_sharding_amd.ops import hip, packing  # noqa: E402
+from llm_sharding_amd.ops import hip, int4, packing  # noqa: E402
 
 DEV = "cuda"
 
@@ -56,7 +56,7 @@ EPIS = {"qkv": hip.EPI_QKV, "o": hip.EPI_RESID, "gate_up": hip.EPI_SWIGLU, "down
         "lm_head": hip.EPI_ARGMAX}
 
 
-def gemv_sweep(out_rows, models, rows_list, tune_entries, fp8=False):
+def gemv_sweep(out_rows, models, rows_list, tune_entries, fp8=False, do_int4=False):
     from llm_sharding_amd.models.rope import rope_table
     from llm_sharding_amd.config import llama2_7b
     cos, sin = rope_table(llama2_7b(), 1024, DEV)
@@ -70,6 +70,14 @@ def gemv_sweep(out_rows, models, rows_list, tune_entries, fp8=False):
                 nbuf8 = max(2, (600 << 20) // (N * K) + 1)
                 q8, s8 = packing.quantize_fp8_rows(torch.randn(N, K, device=DEV).mul_(0.02))
                 w8 = [packing.pack_b_fp8(q8).view(-1).clone() for _ in range(nbuf8)]
+            do4 = do_int4 and epi != hip.EPI_ARGMAX and K % int4.INT4_GROUP == 0  # (the lm_head stays bf16)
+            if do4:
+                nbuf4 = max(2, (600 << 20) // int4.int4_bytes(N, K) + 1)
+                q4, s4 = int4.quantize_int4_groups(torch.randn(N, K, device=DEV).mul_(0.02))
+                s4 = int4.pack_scales_int4(s4)
+                p4 = int4.pack_b_int4(q4)
+                w4 = [p4.clone() for _ in range(nbuf4)]
+                sc4 = [s4.clone() for _ in range(nbuf4)]
             for M in rows_list:
                 x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
                 out = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
@@ -113,6 +121,19 @@ def gemv_sweep(out_rows, models, rows_list, tune_entries, fp8=False):
                     print(json.dumps(line8), flush=True)
                     out_rows.append(line8)
                     tune_entries.setdefault((N, K, packing.row_blocks(M), even, "fp8"), (r8[0][1], list(r8[0][2])))
+                if do4 and M <= int4.INT4_MAX_ROWS:
+                    r4 = []
+                    for cfg in int4.int4_gemv_candidates(N // 16, K, M, even):
+                        us = timeit(lambda i: int4.gemv_int4(x, w4[i % nbuf4], sc4[i % nbuf4], M, N, K, epi, ep, norm=norm,
+                                                            cfg=cfg))
+                        r4.append((us, "int4", cfg, int4.int4_bytes(N, K) / us / 1e6))
+                    r4.sort(key=lambda r: r[0])
+                    line4 = {"kernel": "gemv_int4", "model": model, "shape": name, "N": N, "K": K, "M": M,
+                             "best_us": round(r4[0][0], 2), "best_cfg": list(r4[0][2]), "best_TBps": round(r4[0][3], 2),
+                             "auto_cfg": list(int4.int4_config(N // 16, M, even, K)),
+                             "all": [(round(r[0], 2), r[1]) + tuple(r[2]) for r in r4]}
+                    print(json.dumps(line4), flush=True)
+                    out_rows.append(line4)
                 res.sort(key=lambda r: r[0])
                 best = res[0]
                 line = {"kernel": "gemv", "model": model, "shape": name, "N": N, "K": K, "M": M,
@@ -180,13 +201,14 @@ def main():
     ap.add_argument("--tune-file", default=packing.TUNING_FILE,
                     help="table to write (on a gpurun box: a path under gpurun_out/, then copy it back)")
     ap.add_argument("--fp8", action="store_true", help="also sweep the fp8-weight (W8A16) kernels")
+    ap.add_argument("--int4", action="store_true", help="also sweep the int4-weight (W4A16, group-128) kernel")
     ap.add_argument("--out", default="gpurun_out/bench_kernels.json")
     a = ap.parse_args()
     hip.lib()
     rows = []
     tune = {}
     if "gemv" in a.only:
-        gemv_sweep(rows, a.models.split(","), [int(r) for r in a.rows.split(",")], tune, fp8=a.fp8)
+        gemv_sweep(rows, a.models.split(","), [int(r) for r in a.rows.split(",")], tune, fp8=a.fp8, do_int4=a.int4)
         if a.tune:
             old = {}
             if os.path.exists(packing.TUNING_FILE):
