@@ -55,6 +55,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prompt", default="Write a poem about the blue sky.")
     ap.add_argument("--max-new-tokens", type=int, default=128)
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
+                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per cached vector (GPU)")
     ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
                     help="projection weights on the GPU: bf16, fp8 (OCP e4m3, per-row scales, fp8 lm_head) or int4 "
                          "(symmetric group-128, bf16 lm_head); ignored on the CPU")
@@ -181,7 +183,8 @@ def main(argv=None):
     dt = torch.bfloat16 if a.device.startswith("cuda") else torch.float32
     t0 = time.perf_counter()
     eng = make_stage_engine(cfg, 0, cfg.num_hidden_layers, a.device, dt, has_embed=True, has_head=True, source=src,
-                            max_seq=min(cfg.max_position_embeddings, 4096), weight_dtype=a.weight_dtype)
+                            max_seq=min(cfg.max_position_embeddings, 4096), weight_dtype=a.weight_dtype,
+                            kv_dtype=a.kv_dtype)
     ids = tok(a.prompt, return_tensors="pt")["input_ids"][0]
     if a.choice:
         sp = sampling_from_args(a, [tok.encode(c, add_special_tokens=False) for c in a.choice])

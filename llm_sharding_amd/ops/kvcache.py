@@ -168,6 +168,8 @@ def kv_fork(k_cache, v_cache, jobs, flags: Optional[int] = None) -> None:
 def fork_jobs(eng, jobs) -> None:
     """Run fork ``jobs`` over every layer of ``eng`` (the HIP kernel on a GPU engine, the reference
     elsewhere) and set the destinations' host-side lengths."""
+    if getattr(eng, "kv8", False):
+        raise NotImplementedError("KV fork on an fp8 KV cache: the fork kernel copies bf16 tensors")
     if not eng.k_cache:
         return
     n_slots, _, t_max, _ = eng.k_cache[0].shape

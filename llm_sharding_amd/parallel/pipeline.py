@@ -235,8 +235,9 @@ class PipelineStage:
                  microbatches: int, max_seq: int, source, use_graph: bool = True,
                  max_prefill_rows: int = 2048, dtype=torch.bfloat16, p2p=None,
                  split_head: Optional[bool] = None, weight_dtype: str = "bf16", streams: int = 1,
-                 pp_streams: Optional[bool] = None, engine: Optional[StageEngine] = None):
-        """``engine``: reuse a loaded StageEngine (its weights, KV cache and scratch) instead of
+                 pp_streams: Optional[bool] = None, engine: Optional[StageEngine] = None, kv_dtype: str = "bf16"):
+        """``kv_dtype="fp8"``: an fp8 KV cache on a GPU stage (runtime/engine_kv8.py).
+        ``engine``: reuse a loaded StageEngine (its weights, KV cache and scratch) instead of
         building one - e.g. a batch-1 latency pass after a throughput pass; it must cover this
         stage's layers and hold >= batch x microbatches KV slots."""
         self.cfg, self.rank, self.world = cfg, rank, world
@@ -271,7 +272,7 @@ class PipelineStage:
                                          has_head=self.last or (self.split and self.first), source=source,
                                          max_slots=batch * microbatches, max_seq=max_seq,
                                          max_prefill_rows=max(max_prefill_rows, batch), head_cols=head_cols,
-                                         weight_dtype=weight_dtype)
+                                         weight_dtype=weight_dtype, kv_dtype=kv_dtype)
         H = cfg.hidden_size
         self.h_out = [torch.zeros((batch, H), dtype=self.dtype, device=self.device) for _ in range(microbatches)]
         self.tok_out = [torch.zeros(batch, dtype=torch.int32, device=self.device) for _ in range(microbatches)]
@@ -767,7 +768,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
                          verbose: bool = True, weight_dtype: str = "bf16", streams: int = 1,
                          device: str = "cuda", dp: int = 1, latency_steps: int = 0,
                          stage_layers: int = 0, transport: str = "rccl", mid_batch: int = 0,
-                         collect_outputs: bool = False) -> Optional[dict]:
+                         collect_outputs: bool = False, kv_dtype: str = "bf16") -> Optional[dict]:
     """``microbatches`` 0 = ``streams`` x stages (every GPU holds ``streams`` micro-batches of
     ``batch`` sequences: weak scaling); ``max_seq`` 0 = what the run needs, rounded up to 64.
 
@@ -845,7 +846,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     max_seq = max_seq or -(-need // 64) * 64
     S_sets = max(1, min(streams, M))
     plan = plan_stages(cfg, pp, kv_tokens=max_seq * batch * M, head_split=pp > 1,
-                       scratch=scratch_bytes(cfg, batch * prompt_len, S_sets, max_seq))
+                       scratch=scratch_bytes(cfg, batch * prompt_len, S_sets, max_seq), kv_dtype=kv_dtype)
     st = plan.stages[srank]
     # this stage's device bytes as the engine will allocate them (profiles/memory_table.md)
     V = cfg.head_rows
@@ -853,7 +854,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     head_rows = (v1 if st.has_head else 0) + (V - v1 if (pp > 1 and st.has_embed) else 0)
     mem_pred = stage_memory(cfg, st.n_layers, slots=batch * M, max_seq=max_seq, prefill_rows=batch * prompt_len,
                             has_embed=st.has_embed, head_rows=head_rows, scratch_sets=S_sets, io_rows=batch * M,
-                            weight_dtype=weight_dtype)
+                            weight_dtype=weight_dtype, kv_dtype=kv_dtype)
     if need > max_seq:
         raise ValueError(f"prompt+warmup+steps ({need}) exceeds max_seq {max_seq}")
     if verbose and rank == 0:
@@ -890,7 +891,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     stage = PipelineStage(cfg, srank, pp, st.start, st.end, dev, batch, M, max_seq,
                           RandomSource(cfg, seed), use_graph=use_graph,
                           max_prefill_rows=batch * prompt_len, weight_dtype=weight_dtype, streams=streams,
-                          dtype=torch.bfloat16 if gpu else torch.float32, p2p=p2p)
+                          dtype=torch.bfloat16 if gpu else torch.float32, p2p=p2p, kv_dtype=kv_dtype)
     if dp > 1:  # trace files are named by rank: use the global one
         stage.tl = tracing.from_env(rank, dev if gpu else "cpu")
     sync()

@@ -78,13 +78,15 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
                 layer_costs: Optional[Sequence[float]] = None, embed_cost: Optional[float] = None,
                 head_cost: Optional[float] = None, kv_tokens: int = 0, elem_bytes: int = 2,
                 min_layers: int = 1, head_split: bool = False, scratch: float = 0.0,
-                stage_overhead: float = 0.0) -> Plan:
+                stage_overhead: float = 0.0, kv_dtype: str = "bf16") -> Plan:
     """Exact min-max contiguous partition. ``devices`` is a list (chain order) or a count.
     ``head_split``: the lm_head is shared by the last and the first stage (pipeline.py), so each
     carries half of its cost and memory. ``scratch``: per-stage engine scratch bytes
     (:func:`scratch_bytes`), counted against every device's memory next to weights and KV.
     ``stage_overhead``: fixed cost of one stage step (measured costs:
-    node_profiler.costs_for_planner), added to every stage before its device's speed factor."""
+    node_profiler.costs_for_planner), added to every stage before its device's speed factor.
+    ``kv_dtype="fp8"``: a cached token costs :func:`kv_token_bytes` per layer, and every stage also
+    holds one bf16 staging layer over its ``kv_tokens`` (runtime/engine_kv8.py), counted with its scratch."""
     if isinstance(devices, int):
         devices = [DeviceSpec() for _ in range(devices)]
     n, L = len(devices), cfg.num_hidden_layers
@@ -95,7 +97,9 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
     ec = ec if embed_cost is None else embed_cost
     hc = hc if head_cost is None else head_cost
     lbytes = float(cfg.layer_bytes(elem_bytes))
-    kv_per_layer = float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * kv_tokens
+    kv_per_layer = float(kv_token_bytes(cfg, elem_bytes, kv_dtype)) * kv_tokens
+    if kv_dtype == "fp8":
+        scratch = scratch + float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * kv_tokens
     emb_bytes = float(cfg.vocab_size * cfg.hidden_size * elem_bytes)
     head_bytes = emb_bytes if not cfg.tie_word_embeddings else 0.0
 
@@ -157,14 +161,49 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
     return plan
 
 
+def kv_token_bytes(cfg: LlamaConfig, elem_bytes: int = 2, kv_dtype: str = "bf16") -> int:
+    """Bytes one cached token costs per layer: ``2 * n_kv * hd * elem_bytes``, or with
+    ``kv_dtype="fp8"`` ``n_kv * (2 * hd + 8)`` (8448 against 16384 for Llama-2-7B)."""
+    if kv_dtype == "bf16":
+        return cfg.kv_bytes_per_token_per_layer(elem_bytes)
+    if kv_dtype != "fp8":
+        raise ValueError(f"kv_dtype must be bf16 or fp8, got {kv_dtype!r}")
+    return cfg.num_key_value_heads * (2 * cfg.head_dim + 8)
+
+
+def size_kv_slots(cfg: LlamaConfig, world: int, max_seq: int, mem_bytes: float, reserve_bytes: float,
+                  microbatches: int, prefix_slots: int = 0, kv_dtype: str = "bf16") -> tuple:
+    """(slots per micro-batch, plan): the KV cache of a ``world``-stage server sized from the
+    devices' HBM. The KV budget moves the layer boundaries, so slots and plan are iterated to a
+    fixed point; the prefix pool's slots come out of the same HBM. ``kv_dtype`` prices the cache in
+    both :func:`kv_slots_for_memory` and :func:`plan_stages`."""
+    M = microbatches
+    plan = plan_stages(cfg, world)
+    batch = 1
+    for _ in range(8):
+        batch = min(kv_slots_for_memory(cfg, s.n_layers, max_seq, mem_bytes, s.weight_bytes,
+                                        reserve_bytes=reserve_bytes, microbatches=M, kv_dtype=kv_dtype)
+                    for s in plan.stages)
+        batch = max(1, (batch * M - prefix_slots) // M)
+        nxt = plan_stages(cfg, world, kv_tokens=max_seq * (batch * M + prefix_slots), kv_dtype=kv_dtype)
+        if nxt.ranges() == plan.ranges():
+            break
+        plan = nxt
+    return batch, plan_stages(cfg, world, kv_tokens=max_seq * (batch * M + prefix_slots), kv_dtype=kv_dtype)
+
+
 def kv_slots_for_memory(cfg: LlamaConfig, n_layers: int, max_seq: int, mem_bytes: float,
                         weight_bytes: float, reserve_bytes: float = 8e9, elem_bytes: int = 2,
-                        microbatches: int = 1, max_per_microbatch: int = 128) -> int:
+                        microbatches: int = 1, max_per_microbatch: int = 128, kv_dtype: str = "bf16") -> int:
     """KV slots (sequences of ``max_seq`` tokens) per micro-batch that fit a stage of
     ``n_layers`` layers next to its weights: the static KV cache is sized from the device's
     HBM (288 GB on MI355X) instead of a fixed guess. Capped at
-    ``max_per_microbatch`` (the largest hipGraph decode batch)."""
-    per_slot = float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * n_layers * max_seq
+    ``max_per_microbatch`` (the largest hipGraph decode batch). ``kv_dtype="fp8"``: a token costs
+    ``n_kv * (2 * hd + 8)`` bytes per layer (codes + two fp32 scales, ops/kv8.py), and the one bf16
+    staging layer the fp8 engine keeps is sized with the slots it serves."""
+    per_slot = float(kv_token_bytes(cfg, elem_bytes, kv_dtype)) * n_layers * max_seq
+    if kv_dtype == "fp8":  # one staging layer over all slots
+        per_slot += float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * max_seq
     free = mem_bytes - reserve_bytes - weight_bytes
     if per_slot <= 0 or free < per_slot * microbatches:
         raise ValueError(f"no room for a KV cache of {max_seq} tokens x {n_layers} layers "
@@ -201,7 +240,7 @@ def scratch_bytes(cfg: LlamaConfig, rows: int, sets: int = 1, max_seq: int = 409
 
 def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, prefill_rows: int,
                  has_embed: bool = False, head_rows: int = 0, scratch_sets: int = 1,
-                 io_rows: int = 0, elem_bytes: int = 2, weight_dtype: str = "bf16") -> dict:
+                 io_rows: int = 0, elem_bytes: int = 2, weight_dtype: str = "bf16", kv_dtype: str = "bf16") -> dict:
     """Device bytes of one pipeline stage as the engine allocates them (weights, static KV cache,
     scratch) - the memory table the bench's stage sizing relies on (profiles/memory_table.md).
     ``head_rows``: lm_head rows held on this stage (split head: a part of the vocabulary);
@@ -209,7 +248,9 @@ def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, p
     ``weight_dtype="int4"``: the four projections of a layer at 4.25 bits per weight (nibbles +
     fp32 group-128 scales; embedding, lm_head and norms stay ``elem_bytes``), plus one
     projection-sized bf16 dequantisation buffer per scratch set. Any other value ("fp8" too, which
-    this table never modelled) counts the weights at ``elem_bytes``."""
+    this table never modelled) counts the weights at ``elem_bytes``. ``kv_dtype="fp8"``: ``kv`` counts
+    ``n_kv * (2 * hd + 8)`` bytes per token and layer, and ``scratch`` grows by the one bf16 staging
+    layer (runtime/engine_kv8.py)."""
     H = cfg.hidden_size
     w = n_layers * cfg.layer_bytes(elem_bytes)
     w_scratch = 0
@@ -222,8 +263,10 @@ def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, p
         w += cfg.vocab_size * H * elem_bytes
     if head_rows:
         w += head_rows * H * elem_bytes + H * elem_bytes          # lm_head part + final norm
-    kv = n_layers * cfg.kv_bytes_per_token_per_layer(elem_bytes) * slots * max_seq
+    kv = n_layers * kv_token_bytes(cfg, elem_bytes, kv_dtype) * slots * max_seq
     scratch = scratch_bytes(cfg, prefill_rows, scratch_sets, max_seq, head_rows) + w_scratch
+    if kv_dtype == "fp8":
+        scratch += cfg.kv_bytes_per_token_per_layer(elem_bytes) * slots * max_seq
     io = io_rows * (H * elem_bytes + 4 + 8)
     return {"weights": float(w), "kv": float(kv), "scratch": float(scratch), "io": float(io),
             "total": float(w + kv + scratch + io)}

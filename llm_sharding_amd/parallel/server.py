@@ -163,8 +163,13 @@ class PipelineServer:
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
                  ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
                  prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256,
-                 vocab_bytes=None, dfa_rows: int = 4096):
+                 vocab_bytes=None, dfa_rows: int = 4096, kv_dtype: str = "bf16"):
         self.cfg, self.rank, self.world = cfg, rank, world
+        from ..runtime.engine_kv8 import check_kv_dtype
+        check_kv_dtype(kv_dtype)
+        if kv_dtype == "fp8" and int(prefix_slots) > 0:
+            raise ValueError("prefix_slots > 0 needs kv_dtype='bf16': the KV fork kernel copies bf16 tensors")
+        self.kv_dtype = kv_dtype
         # prefix pool: engine slots >= B * M, never decoded, in no micro-batch and no graph
         self.P = int(prefix_slots)
         if self.P < 0 or int(prefix_min_match) < 1:
@@ -237,9 +242,11 @@ class PipelineServer:
 
     # ------------------------------------------------------------------ engine (re)build
     def _build_engine(self, start: int, end: int) -> StageEngine:
-        return StageEngine(self.cfg, start, end, self.device, self.dtype, has_embed=self.first, has_head=self.last,
-                           source=self.source, max_slots=self.B * self.M + self.P, max_seq=self.max_seq,
-                           max_prefill_rows=max(self.budget, self.B), causal=self.causal)
+        from ..runtime.engine_int4 import make_stage_engine
+        return make_stage_engine(self.cfg, start, end, self.device, self.dtype, has_embed=self.first,
+                                 has_head=self.last, source=self.source, max_slots=self.B * self.M + self.P,
+                                 max_seq=self.max_seq, max_prefill_rows=max(self.budget, self.B), causal=self.causal,
+                                 kv_dtype=self.kv_dtype)
 
     def _build_graphs(self) -> None:
         for k in range(1, self.S):

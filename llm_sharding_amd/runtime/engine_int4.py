@@ -255,9 +255,15 @@ class Int4StageEngine(StageEngine):
 
 
 def make_stage_engine(cfg, start: int, end: int, device="cpu", dtype=torch.bfloat16, *, weight_dtype: str = "bf16",
-                      **kw) -> StageEngine:
+                      kv_dtype: str = "bf16", **kw) -> StageEngine:
     """``StageEngine`` for ``weight_dtype`` "bf16" / "fp8" (anything else raises there),
-    ``Int4StageEngine`` for "int4"."""
+    ``Int4StageEngine`` for "int4"; ``kv_dtype="fp8"`` on a GPU: ``Fp8KVStageEngine``
+    (runtime/engine_kv8.py; bf16 or fp8 weights). A CPU engine ignores ``kv_dtype`` as it ignores
+    ``weight_dtype``; a value other than "bf16" / "fp8" raises on every device."""
+    from .engine_kv8 import Fp8KVStageEngine, check_kv_dtype
+    check_kv_dtype(kv_dtype, weight_dtype)
+    if kv_dtype == "fp8" and torch.device(device).type == "cuda":
+        return Fp8KVStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)
     if weight_dtype == "int4":
         return Int4StageEngine(cfg, start, end, device, dtype, **kw)
     return StageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)

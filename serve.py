@@ -99,6 +99,9 @@ def main():
     ap.add_argument("--shared-prefix-len", type=int, default=0, metavar="L",
                     help="load test: every request starts with the same L tokens and declares them")
     ap.add_argument("--n", type=int, default=1, metavar="N", help="load test: N samples per prompt (submit_n)")
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
+                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per cached vector "
+                         "(8448 instead of 16384 bytes per Llama-2-7B token and layer; no --prefix-slots)")
     argv = sys.argv[1:]
     for i in range(len(argv) - 1):  # a pattern that starts with '-' is no option
         if argv[i] == "--regex":
@@ -131,21 +134,14 @@ def main():
     cfg, source = rc.model_and_source()
     M = rc.microbatches or max(2, world)
     if rc.batch == 0:  # size the KV cache from this GPU's HBM
-        from llm_sharding_amd.parallel.scheduler import kv_slots_for_memory, scratch_bytes
+        from llm_sharding_amd.parallel.scheduler import scratch_bytes, size_kv_slots
         mem = torch.cuda.get_device_properties(dev).total_memory if gpu else 64e9
         # activations / workspaces of every concurrently replayed scratch set, plus 8 GB slack
         reserve = 8e9 + scratch_bytes(cfg, rc.prefill_budget, sets=max(1, rc.streams))
-        plan = plan_stages(cfg, world)
-        for _ in range(8):  # the KV budget moves layer boundaries: iterate to a fixed point
-            rc.batch = min(kv_slots_for_memory(cfg, s.n_layers, rc.max_seq, mem, s.weight_bytes, reserve_bytes=reserve,
-                                               microbatches=M) for s in plan.stages)
-            rc.batch = max(1, (rc.batch * M - a.prefix_slots) // M)  # the pool's slots come out of the same HBM
-            nxt = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots))
-            if nxt.ranges() == plan.ranges():
-                break
-            plan = nxt
+        # (the KV budget moves layer boundaries: iterated to a fixed point, priced by the cache format)
+        rc.batch, _ = size_kv_slots(cfg, world, rc.max_seq, mem, reserve, M, a.prefix_slots, a.kv_dtype)
         log.info(f"KV cache sized from {mem / 1e9:.0f} GB HBM: {rc.batch} slots x {M} micro-batches")
-    plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots))
+    plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots), kv_dtype=a.kv_dtype)
     st = plan.stages[rank]
     if rank == 0:
         log.info(f"{cfg.name}: {world} stage(s) {plan.ranges()}, {M} x {rc.batch} slots")
@@ -169,7 +165,7 @@ def main():
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
                          streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows,
-                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows)
+                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows, kv_dtype=a.kv_dtype)
     if rank != 0:
         srv.serve()
     elif a.requests:
