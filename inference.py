@@ -17,6 +17,8 @@ constrain the output on the device (``ops.constraints``); not together with ``--
 ``--speculative K [--spec-ngram MIN,MAX]`` decodes speculatively: K tokens drafted from the sequence's
 own history (the longest n-gram match of MIN..MAX tokens) are verified in one step of K + 1 rows; the
 output is the plain output, greedy or sampled, in fewer steps when the text repeats itself.
+``--speculative K --draft-shards DIR`` (or ``--draft-random PRESET`` beside ``--random``) drafts with a
+second, smaller model of the same vocabulary instead (``--spec-ngram`` is ignored then).
 
     python inference.py --shards DIR [--prompt "..."] [--max-new-tokens 128]
     python inference.py --random llama2-7b --max-new-tokens 64     # random-init weights
@@ -28,6 +30,8 @@ output is the plain output, greedy or sampled, in fewer steps when the text repe
     python inference.py --shards DIR --choice " yes" --choice " no" --choice " maybe"
     python inference.py --shards DIR --temperature 0.8 --min-p 0.05 --min-tokens 16 --ban 13
     python inference.py --shards DIR --speculative 3 [--temperature 0.7 --top-p 0.9 --seed 1]
+    python inference.py --shards DIR --speculative 3 --draft-shards SMALL_DIR
+    python inference.py --random llama2-7b --speculative 3 --draft-random llama2-7b-2l
 
 ``--hf-compare HF_DIR`` also runs what the reference's inference.py runs
 (/root/reference/inference.py:16-45: transformers' AutoModelForCausalLM + greedy generate) on the
@@ -94,13 +98,45 @@ def build_parser() -> argparse.ArgumentParser:
                     help="speculative decoding: verify K (1..15) n-gram drafts per step (0: off)")
     ap.add_argument("--spec-ngram", default="1,3", metavar="MIN,MAX",
                     help="n-gram lengths (1 <= MIN <= MAX <= 8) of the draft lookup")
+    ap.add_argument("--draft-shards", default="", metavar="DIR",
+                    help="with --speculative: draft with the model in DIR (same vocabulary) instead of the n-gram "
+                         "lookup; --spec-ngram is ignored then")
+    ap.add_argument("--draft-random", default="", metavar="PRESET",
+                    help="with --speculative: a random-init draft model (seed 1) of preset PRESET, beside --random")
+    ap.add_argument("--draft-weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
+                    help="the draft model's projection weights on the GPU")
     return ap
+
+
+def draft_engine_from_args(a, eng):
+    """--draft-shards / --draft-random (``speculative_from_args`` has checked them against the other
+    flags): None without either, else the draft model whole on one stage of ``eng``'s device, with
+    its sequence length and one slot."""
+    if not (a.draft_shards or a.draft_random):
+        return None
+    if a.draft_shards:
+        cfg = LlamaConfig.from_pretrained(a.draft_shards)
+        src = ShardFolderSource(a.draft_shards, cfg)
+    else:
+        cfg = get_preset(a.draft_random)
+        src = RandomSource(cfg, 1)
+    if cfg.vocab_size != eng.cfg.vocab_size:
+        raise SystemExit(f"[ERROR] the draft model's vocab_size {cfg.vocab_size} is not the target's {eng.cfg.vocab_size}")
+    if cfg.max_position_embeddings < eng.max_seq:
+        raise SystemExit(f"[ERROR] the draft model's {cfg.max_position_embeddings} positions are fewer than the "
+                         f"target's max_seq {eng.max_seq}")
+    return make_stage_engine(cfg, 0, cfg.num_hidden_layers, a.device, eng.dtype, has_embed=True, has_head=True,
+                             source=src, max_seq=eng.max_seq, weight_dtype=a.draft_weight_dtype)
 
 
 def speculative_from_args(a, sp):
     """--speculative / --spec-ngram: None without the flag, else (k, (nmin, nmax)); exits on a value
     out of range or a flag speculation does not combine with."""
+    if a.draft_shards and a.draft_random:
+        raise SystemExit("[ERROR] --draft-shards and --draft-random are two draft models: pass one")
     if a.speculative == 0:
+        if a.draft_shards or a.draft_random:
+            raise SystemExit("[ERROR] --draft-shards / --draft-random need --speculative K")
         return None
     from llm_sharding_amd.ops.speculative import MAX_K, MAX_NGRAM
     if not 1 <= a.speculative <= MAX_K:
@@ -191,12 +227,19 @@ def main(argv=None):
     print(f"[INFO] loaded in {time.perf_counter() - t0:.1f}s; prompt tokens {ids.numel()}")
     if a.score:
         return score(eng, tok, ids.tolist())
+    draft = draft_engine_from_args(a, eng)
     slot, pos = eng.prefill_rows([0], [ids.numel()])
     h = eng.forward(eng.embed(ids.to(a.device)), slot, pos)
     eng.advance([0], [ids.numel()])
     if spec is not None:
-        out, dt_s, st = speculative_tokens(eng, h, ids.tolist(), a.max_new_tokens, spec[0], spec[1], sp, cfg.eos_ids)
+        out, dt_s, st = speculative_tokens(eng, h, ids.tolist(), a.max_new_tokens, spec[0], spec[1], sp, cfg.eos_ids,
+                                           draft=draft)
         out = report(a, cfg, tok, ids, out, dt_s)
+        if draft is not None:
+            print(f"[INFO] speculative k={spec[0]} draft model {draft.cfg.name} ({draft.n_layers} layers, "
+                  f"{a.draft_weight_dtype}): {st['tokens']} tokens in {st['steps']} steps, "
+                  f"{st['tokens'] / max(1, st['steps']):.2f} tokens per step")
+            return out
         print(f"[INFO] speculative k={spec[0]} n-gram {spec[1][0]}..{spec[1][1]}: {st['tokens']} tokens in {st['steps']} "
               f"steps, {st['tokens'] / max(1, st['steps']):.2f} tokens per step, a draft matched in {st['matched']} steps")
         return out
@@ -255,11 +298,12 @@ def print_logprobs(tok, out: list, lp: dict) -> None:
               + (f"  top [{alts}]" if alts else ""))
 
 
-def speculative_tokens(eng, h, ids: list, n_new: int, k: int, ngram: tuple, sp, eos_ids) -> tuple:
+def speculative_tokens(eng, h, ids: list, n_new: int, k: int, ngram: tuple, sp, eos_ids, draft=None) -> tuple:
     """Speculative continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from the head (``Sampler.sample`` when sampling), the rest from a
     captured ``SpecDecodeGraph`` on the GPU (the eager twin on the CPU), replayed until the sequence
-    is done. Returns (tokens, seconds, {steps, tokens, matched})."""
+    is done. ``draft``: a draft engine instead of the n-gram lookup (its slot 0 is prefilled by
+    ``admit``). Returns (tokens, seconds, {steps, tokens, matched})."""
     from llm_sharding_amd.runtime.sampling import Sampler
     from llm_sharding_amd.runtime.speculative import EagerSpecDecode, SpecDecodeGraph
     if sp is None:
@@ -269,7 +313,7 @@ def speculative_tokens(eng, h, ids: list, n_new: int, k: int, ngram: tuple, sp, 
         first = Sampler(eng).sample(h, [len(ids) - 1], [sp], [len(ids)])
     t1 = time.perf_counter()
     g = (SpecDecodeGraph if eng.gpu else EagerSpecDecode)(eng, 1, k, ngram=ngram, sampling=sp is not None,
-                                                          history_len=max(1, n_new), eos_ids=eos_ids)
+                                                          history_len=max(1, n_new), eos_ids=eos_ids, draft=draft)
     try:
         g.admit(0, ids + [int(first[0])], n_new, sp)
     except ValueError as e:

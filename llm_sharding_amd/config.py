@@ -231,6 +231,8 @@ def tiny_gpt2(layers: int = 4, hidden: int = 256, heads: int = 4, vocab: int = 5
 
 PRESETS = {
     "llama2-7b": llama2_7b,
+    # two layers of the 7B's width and vocabulary: a random-init draft model for speculative decoding
+    "llama2-7b-2l": lambda: LlamaConfig(num_hidden_layers=2, name="Llama-2-7b-2L"),
     "llama2-13b": llama2_13b,
     "llama2-70b": llama2_70b,
     "llama3.2-3b": llama32_3b,

@@ -33,6 +33,26 @@ not done whose ``matched`` is non-zero.
 ``m <= 0``, then ``m = 0``) gives ``done = 1``; ``hist[s, L:L+m] = cand[r0:r0+m]``, ``hlen[s] = L + m``,
 ``n_acc[s] = m``, ``acc_history[step, s] = m`` (``step = step_ctr[0] < len(acc_history)``);
 ``step_ctr[0] += 1`` per call. Nothing else is written.
+
+**Draft model** (csrc/spec/spec_draft_model.hip; :func:`draft_model_reference`). The drafts come
+from a second, smaller engine of the same vocabulary, run greedily inside the step; accept is
+unchanged. ``dmax`` is the draft engine's ``max_seq`` (``>= max_seq``).
+
+1. Invariant: before a step the draft engine's slot holds valid K/V for positions ``[0, L - 2)`` at
+   least (``admit`` prefills it with ``hist[0:L-1]``).
+2. Iteration 0, two draft rows per sequence: ``hist[pa]`` at ``pa = max(L - 2, 0)`` and ``hist[L-1]``
+   at ``L - 1`` (``L == 1``: the same row twice); ``d[0]`` = the arg-max of the second row. Two rows
+   are always enough: the previous step (length ``L'``) fed the draft positions ``L' - 2 .. L' + k - 2``
+   and ``L <= L' + a + 1`` after ``a <= k`` accepted drafts, so only position ``L - 2`` can be missing,
+   and only when ``a == k``; rewriting a valid cell is harmless.
+3. Iterations ``j = 1 .. k-1``, one draft row per sequence: ``d[j-1]`` at ``L - 1 + j``; its arg-max
+   is ``d[j]``. Draft positions are clamped into ``[0, dmax)`` (a no-op while ``limit + k <= max_seq``).
+4. Target rows as in script mode: row 0 ``hist[L-1]`` at ``L - 1``, row ``j + 1`` ``d[j]`` at ``L + j``,
+   ``matched[s] = 1``, ``match_ctr[s] += 1`` unless done. A done sequence is drafted like any other.
+
+``lsa_spec_dm_begin`` writes iteration 0's draft rows (token, position, slot), the target's row-0
+token and all ``k + 1`` target positions; ``lsa_spec_dm_chain(j)`` writes ``d[j]`` into the target's
+row ``j + 1`` and, while ``j + 1 < k``, the draft's next row (token and position).
 """
 from __future__ import annotations
 
@@ -165,6 +185,79 @@ def accept_reference(hist, hlen, limit, done, eos, tokens, cand, k: int, max_seq
     return n_acc
 
 
+def check_draft_shape(n_seq: int, k: int, ld: int, max_seq: int, draft_max_seq: int) -> None:
+    check_shape(n_seq, k, ld, max_seq)
+    if draft_max_seq < max_seq:
+        raise ValueError(f"speculative: the draft engine's max_seq {draft_max_seq} is below the target's {max_seq}")
+
+
+def _draft_pos(p: int, dmax: int) -> int:
+    return min(max(int(p), 0), dmax - 1)
+
+
+def dm_begin_reference(hist, hlen, slots, k: int, max_seq: int, draft_max_seq: int, done=None, match_ctr=None) -> dict:
+    """``lsa_spec_dm_begin`` in numpy: ``d_tokens`` / ``d_pos`` / ``d_slot`` int32 [2 * n_seq] (the
+    draft engine's catch-up rows), ``tokens`` / ``pos`` int32 [n_seq * (k + 1)] (of ``tokens`` only
+    row 0 of every sequence is written: the others are returned as 0) and ``matched`` int32
+    [n_seq]. ``match_ctr`` (an int32 numpy array) is updated in place."""
+    hist, hlen, slots = _np(hist), _np(hlen), _np(slots)
+    n_seq, ld = hist.shape
+    check_draft_shape(n_seq, k, ld, max_seq, draft_max_seq)
+    out = {"d_tokens": np.zeros(2 * n_seq, dtype=np.int32), "d_pos": np.zeros(2 * n_seq, dtype=np.int32),
+           "d_slot": np.zeros(2 * n_seq, dtype=np.int32), "tokens": np.zeros(n_seq * (k + 1), dtype=np.int32),
+           "pos": np.zeros(n_seq * (k + 1), dtype=np.int32), "matched": np.ones(n_seq, dtype=np.int32)}
+    for s in range(n_seq):
+        L = _clamp_len(hlen[s], ld)
+        pa, r0 = max(L - 2, 0), s * (k + 1)
+        out["d_tokens"][2 * s:2 * s + 2] = hist[s, pa], hist[s, L - 1]
+        out["d_pos"][2 * s:2 * s + 2] = _draft_pos(pa, draft_max_seq), _draft_pos(L - 1, draft_max_seq)
+        out["d_slot"][2 * s:2 * s + 2] = slots[s]
+        out["tokens"][r0] = hist[s, L - 1]
+        out["pos"][r0:r0 + k + 1] = L - 1 + np.arange(k + 1)
+        if match_ctr is not None and not (done is not None and _np(done)[s]):
+            match_ctr[s] += 1
+    return out
+
+
+def dm_chain_reference(amax, hlen, ld: int, k: int, j: int, max_seq: int, draft_max_seq: int, tokens: np.ndarray):
+    """``lsa_spec_dm_chain`` in numpy: iteration ``j``'s arg-max tokens ``amax`` [n_seq] go into
+    ``tokens`` (in place, row ``j + 1`` of every sequence); returns the draft engine's next rows
+    ``(d_tokens1, d_pos1)`` int32 [n_seq], or None when ``j + 1 == k``."""
+    amax, hlen = _np(amax), _np(hlen)
+    n_seq = amax.shape[0]
+    check_draft_shape(n_seq, k, ld, max_seq, draft_max_seq)
+    if not 0 <= j < k:
+        raise ValueError(f"speculative: draft iteration {j} outside [0, {k})")
+    tokens[np.arange(n_seq) * (k + 1) + j + 1] = amax
+    if j + 1 == k:
+        return None
+    d_pos1 = np.array([_draft_pos(_clamp_len(hlen[s], ld) + j, draft_max_seq) for s in range(n_seq)], dtype=np.int32)
+    return amax.astype(np.int32), d_pos1
+
+
+def draft_model_reference(hist, hlen, k: int, max_seq: int, draft_max_seq: int, draft_step, slots=None, done=None,
+                          match_ctr=None):
+    """The draft-model contract in numpy (module docstring, **Draft model**). ``draft_step(tokens,
+    pos, slot, out_rows)`` runs the draft engine on the given rows (int32 arrays of one length: two
+    rows per sequence on iteration 0, then one) and returns the greedy token of each row of
+    ``out_rows``, one per sequence. ``slots`` (default ``0 .. n_seq - 1``): the KV slot per sequence.
+    Returns ``(tokens, pos, matched, fed)``: the target's rows as :func:`draft_reference` returns
+    them and ``fed``, the ``(tokens, pos, slot)`` of every draft iteration in order."""
+    n_seq = _np(hist).shape[0]
+    ld = _np(hist).shape[1]
+    slots = np.arange(n_seq, dtype=np.int32) if slots is None else _np(slots).astype(np.int32)
+    b = dm_begin_reference(hist, hlen, slots, k, max_seq, draft_max_seq, done, match_ctr)
+    tokens, fed = b["tokens"], []
+    d_tok, d_pos, d_slot, out_rows = b["d_tokens"], b["d_pos"], b["d_slot"], np.arange(n_seq) * 2 + 1
+    for j in range(k):
+        fed.append((d_tok.copy(), d_pos.copy(), d_slot.copy()))
+        amax = np.asarray(draft_step(d_tok, d_pos, d_slot, out_rows), dtype=np.int32).reshape(n_seq)
+        nxt = dm_chain_reference(amax, hlen, ld, k, j, max_seq, draft_max_seq, tokens)
+        if nxt is not None:
+            (d_tok, d_pos), d_slot, out_rows = nxt, slots, np.arange(n_seq)
+    return tokens, b["pos"], b["matched"], fed
+
+
 # ------------------------------------------------------------------------------ HIP bindings
 _declared = None
 
@@ -182,6 +275,12 @@ def _lib() -> ctypes.CDLL:
         L.lsa_spec_draft.restype = i
         L.lsa_spec_accept.argtypes = [vp, ll, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, i, i, vp, vp]
         L.lsa_spec_accept.restype = i
+        if not hasattr(L, "lsa_spec_dm_begin"):
+            raise RuntimeError("the kernel library has no lsa_spec_dm_begin: rebuild it (python csrc/build.py)")
+        L.lsa_spec_dm_begin.argtypes = [vp, ll, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.lsa_spec_dm_begin.restype = i
+        L.lsa_spec_dm_chain.argtypes = [vp, vp, ll, i, i, i, i, i, vp, vp, vp, vp]
+        L.lsa_spec_dm_chain.restype = i
         _declared = L
     return L
 
@@ -256,5 +355,47 @@ def spec_accept(hist: torch.Tensor, hlen: torch.Tensor, limit: torch.Tensor, don
     _status(rc, "lsa_spec_accept")
 
 
-__all__ = ["MAX_K", "MAX_NGRAM", "MAX_ROWS", "N_EOS", "check_shape", "eos_array", "draft_reference", "accept_reference",
-           "spec_draft", "spec_accept"]
+def spec_dm_begin(hist: torch.Tensor, hlen: torch.Tensor, slots: torch.Tensor, k: int, max_seq: int, draft_max_seq: int,
+                  d_tokens: torch.Tensor, d_pos: torch.Tensor, d_slot: torch.Tensor, tokens: torch.Tensor,
+                  pos: torch.Tensor, matched: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                  match_ctr: Optional[torch.Tensor] = None) -> None:
+    """``lsa_spec_dm_begin`` on the current stream: the draft engine's two catch-up rows per
+    sequence and the target's row 0 and positions. No host reads: graph-capturable."""
+    from .hip import _p, _stream
+    n_seq = hist.shape[0] if hist is not None and hist.dim() == 2 else 0
+    ld = _chk_rows(hist, n_seq, "hist")
+    rows = n_seq * (k + 1)
+    for t, n, what in ((hlen, n_seq, "hlen"), (slots, n_seq, "slots"), (d_tokens, 2 * n_seq, "d_tokens"),
+                       (d_pos, 2 * n_seq, "d_pos"), (d_slot, 2 * n_seq, "d_slot"), (tokens, rows, "tokens"),
+                       (pos, rows, "pos")):
+        _chk(t, n, what)
+    _chk(matched, n_seq, "matched", True)
+    _chk(done, n_seq, "done", True)
+    _chk(match_ctr, n_seq, "match_ctr", True)
+    rc = _lib().lsa_spec_dm_begin(_p(hist), ld, _p(hlen), _p(slots), n_seq, int(k), int(max_seq), int(draft_max_seq),
+                                  _p(d_tokens), _p(d_pos), _p(d_slot), _p(tokens), _p(pos), _p(matched), _p(done),
+                                  _p(match_ctr), _stream())
+    _status(rc, "lsa_spec_dm_begin")
+
+
+def spec_dm_chain(amax: torch.Tensor, hlen: torch.Tensor, ld: int, k: int, j: int, max_seq: int, draft_max_seq: int,
+                  tokens: torch.Tensor, d_tokens1: Optional[torch.Tensor] = None,
+                  d_pos1: Optional[torch.Tensor] = None) -> None:
+    """``lsa_spec_dm_chain`` on the current stream: iteration ``j``'s arg-max tokens into the
+    target's rows ``j + 1`` and (``j + 1 < k``) into the draft engine's next 1-row input."""
+    from .hip import _p, _stream
+    n_seq = hlen.numel() if hlen is not None else 0
+    last = j + 1 >= k
+    _chk(hlen, max(n_seq, 1), "hlen")
+    _chk(amax, n_seq, "amax")
+    _chk(tokens, n_seq * (k + 1), "tokens")
+    _chk(d_tokens1, n_seq, "d_tokens1", last)
+    _chk(d_pos1, n_seq, "d_pos1", last)
+    rc = _lib().lsa_spec_dm_chain(_p(amax), _p(hlen), int(ld), n_seq, int(k), int(j), int(max_seq), int(draft_max_seq),
+                                  _p(tokens), _p(d_tokens1), _p(d_pos1), _stream())
+    _status(rc, "lsa_spec_dm_chain")
+
+
+__all__ = ["MAX_K", "MAX_NGRAM", "MAX_ROWS", "N_EOS", "check_shape", "check_draft_shape", "eos_array", "draft_reference",
+           "accept_reference", "dm_begin_reference", "dm_chain_reference", "draft_model_reference", "spec_draft",
+           "spec_accept", "spec_dm_begin", "spec_dm_chain"]

@@ -21,6 +21,17 @@ exists: the output is the plain output, token for token (given the same kernel n
 * :class:`EagerSpecDecode` - the same interface over ``eng.embed / forward / head`` and the numpy
   references: what CPU engines run, and the graph's twin in tests on a GPU engine.
 * :func:`generate_speculative` - prefill and speculative steps to completion.
+
+**A draft model** (``draft=``): the drafts come from a second, smaller :class:`StageEngine` of the
+same vocabulary, run greedily inside the same step (``ops.speculative``, **Draft model**):
+
+    ``dm_begin -> [draft embed -> layers -> head -> argmax_finalize -> dm_chain] x k -> embed -> ..``
+
+Iteration 0 feeds the draft two rows per sequence (the last two known tokens: at most one of the
+draft's cells is missing after a step that accepted every draft), the others one. Acceptance stays
+token equality against the target's own (greedy or sampled) token, so whatever the draft proposes
+the output is the target's plain output; a better draft only makes the steps fewer. The draft's
+static cache is addressed by position like the target's: nothing is rolled back.
 """
 from __future__ import annotations
 
@@ -42,7 +53,7 @@ class _SpecState:
     its rows rewrite cells no admitted sequence can ever rely on, since ``limit + k <= max_seq``)."""
 
     def __init__(self, eng: StageEngine, n_seq: int, k: int, slots, ngram, script: bool, sampling: bool,
-                 history_len: int, eos_ids):
+                 history_len: int, eos_ids, draft: Optional[StageEngine] = None):
         _check_full_head(eng)
         if not eng.has_embed:
             raise RuntimeError("[ERROR] speculative decoding needs the stage that owns the embedding")
@@ -65,6 +76,47 @@ class _SpecState:
         self.params = [GREEDY] * self.n_seq
         self.prompt_len = [0] * self.n_seq
         self.limits = [0] * self.n_seq
+        self.draft = draft
+        if draft is not None:
+            self._check_draft(draft)
+
+    def _check_draft(self, d: StageEngine) -> None:
+        """The refusals of a draft engine, each naming what does not fit."""
+        eng = self.eng
+        if self.use_script:
+            raise ValueError("speculative: draft= and script=True are two draft sources: pass one of them")
+        if d is eng:
+            raise ValueError("speculative: the draft must be an engine of its own (its KV cache holds the draft "
+                             "model's K/V), not the target engine itself")
+        if d.start != 0 or d.end != d.cfg.num_hidden_layers:
+            raise ValueError(f"speculative: the draft must hold all its layers on one stage, this one holds "
+                             f"[{d.start}, {d.end}) of {d.cfg.num_hidden_layers}")
+        if not d.has_embed or d.embed_w is None:
+            raise ValueError("speculative: the draft engine has no embedding")
+        if d.lm_head is None:
+            raise ValueError("speculative: the draft engine has no lm_head")
+        if (d.head_v0, d.head_v1) != (0, d.cfg.head_rows):
+            raise ValueError(f"speculative: the draft needs its whole lm_head, this one holds vocabulary rows "
+                             f"[{d.head_v0}, {d.head_v1}) of {d.cfg.head_rows} (head_cols)")
+        if d.cfg.vocab_size != eng.cfg.vocab_size:
+            raise ValueError(f"speculative: the draft's vocab_size {d.cfg.vocab_size} is not the target's "
+                             f"{eng.cfg.vocab_size}")
+        if d.max_seq < self.max_seq:
+            raise ValueError(f"speculative: the draft's max_seq {d.max_seq} is below the target's {self.max_seq}")
+        if any(s >= d.max_slots for s in self.slots):
+            raise ValueError(f"speculative: slots {self.slots} outside the draft engine's {d.max_slots}")
+        if d.device != eng.device:
+            raise ValueError(f"speculative: the draft is on {d.device}, the target on {eng.device}")
+
+    def _prefill_draft(self, slot: int, toks: np.ndarray) -> None:
+        """The draft engine's slot from scratch: K/V of ``toks`` at positions ``0 .. len - 1``."""
+        d = self.draft
+        d.reset([slot])
+        for c0 in range(0, int(toks.size), d.max_prefill_rows):
+            chunk = toks[c0:c0 + d.max_prefill_rows]
+            srow, pos = d.prefill_rows([slot], [int(chunk.size)])
+            d.forward(d.embed(torch.from_numpy(chunk.astype(np.int64))), srow, pos)
+            d.advance([slot], [int(chunk.size)])
 
     # the two implementations write one sequence's state
     def _put(self, i: int, hist_row: np.ndarray, hlen: int, limit: int, done: int) -> None:
@@ -87,7 +139,8 @@ class _SpecState:
         prompt plus the first generated token, as a prefill and its head leave them; ``n_prompt``
         (default ``len(tokens) - 1``) says how many of them are the prompt - ``len(tokens)`` for a
         prompt prefilled up to its last token, whose first new token the first step produces.
-        At most ``max_new_tokens`` tokens follow the prompt: ``limit = n_prompt + max_new_tokens``."""
+        At most ``max_new_tokens`` tokens follow the prompt: ``limit = n_prompt + max_new_tokens``.
+        With a draft engine its slot is prefilled here with all but the last of ``tokens``."""
         if not 0 <= i < self.n_seq:
             raise ValueError(f"speculative: sequence {i} outside [0, {self.n_seq})")
         toks = self._check_tokens(tokens, "a prompt")
@@ -121,6 +174,8 @@ class _SpecState:
         row[:n] = toks
         done = int(limit == n or (n > n_prompt and int(toks[-1]) in {int(t) for t in self.eos_np if t >= 0}))
         self.params[i], self.prompt_len[i], self.limits[i] = p, n_prompt, limit
+        if self.draft is not None:
+            self._prefill_draft(slot, toks[:n - 1])
         self._put(i, row, n, limit, done)
 
     def set_script(self, i: int, tokens) -> None:
@@ -154,6 +209,8 @@ class _SpecState:
         for i, s in enumerate(self.slots):
             if self.prompt_len[i]:  # parked sequences leave their slot's length alone
                 self.eng.seq_len[s] = int(hlen[i]) - 1
+                if self.draft is not None:  # the cells the invariant vouches for
+                    self.draft.seq_len[s] = max(0, int(hlen[i]) - 2)
 
 
 class SpecDecodeGraph(_SpecState):
@@ -168,14 +225,23 @@ class SpecDecodeGraph(_SpecState):
     lookup drafts; ``script=True``: drafts from :meth:`set_script` (the hook for an external draft
     source). ``history_len``: steps of accepted counts kept on the device. Admit the sequences, then
     :meth:`capture`, then :meth:`replay` any number of times without a host sync; replays after
-    every sequence is done change nothing but scratch."""
+    every sequence is done change nothing but scratch.
+
+    ``draft=``: a whole model on one stage (all layers, embedding, the whole lm_head; any
+    ``weight_dtype``) with the target's ``vocab_size``, ``max_seq`` at least the target's and the
+    graph's slot ids; ``lsa_spec_draft`` is replaced by ``lsa_spec_dm_begin`` and ``k`` greedy draft
+    iterations on the same stream (module docstring), on two scratch sets of the draft engine's own
+    (2 rows and 1 row per sequence). ``ngram`` is ignored then; ``script=True`` is refused."""
+
+    DRAFT_SCRATCH = ("spec-draft-2", "spec-draft-1")  # StageEngine.decode_scratch keys of the draft engine
 
     def __init__(self, eng: StageEngine, n_seq: int, k: int, slots: Optional[list] = None, ngram=(1, 3),
-                 script: bool = False, sampling: bool = False, history_len: int = 0, eos_ids=()):
+                 script: bool = False, sampling: bool = False, history_len: int = 0, eos_ids=(),
+                 draft: Optional[StageEngine] = None):
         from ..ops import hip
         if not eng.gpu:
             raise RuntimeError("SpecDecodeGraph needs a GPU stage (EagerSpecDecode runs on the CPU)")
-        super().__init__(eng, n_seq, k, slots, ngram, script, sampling, history_len, eos_ids)
+        super().__init__(eng, n_seq, k, slots, ngram, script, sampling, history_len, eos_ids, draft)
         dev, n, rows = eng.device, self.n_seq, self.rows
         i32 = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)  # noqa: E731
         park = self.max_seq - self.k
@@ -197,6 +263,15 @@ class SpecDecodeGraph(_SpecState):
                 setattr(self, name, v)
         self.graph = None
         self._hip = hip
+        if draft is not None:
+            self.slots_t = torch.tensor(self.slots, dtype=torch.int32, device=dev)
+            self.d_tokens, self.d_pos, self.d_slot = i32(2 * n), i32(2 * n), i32(2 * n)
+            self.d_slot.copy_(self.slots_t.repeat_interleave(2))  # what lsa_spec_dm_begin rewrites every step
+            self.d_tokens1, self.d_pos1, self.d_amax = i32(n), i32(n), i32(n)
+            self.d_last = torch.arange(1, 2 * n, 2, dtype=torch.int32, device=dev)  # each pair's second row
+            self.d_keys = torch.zeros(n, dtype=torch.int64, device=dev)
+            for key in self.DRAFT_SCRATCH:
+                draft.decode_scratch(key)  # allocated before any capture
 
     def _put(self, i, hist_row, hlen, limit, done) -> None:
         self.hist[i].copy_(torch.from_numpy(hist_row))
@@ -216,8 +291,11 @@ class SpecDecodeGraph(_SpecState):
 
     def _step(self) -> None:
         hip, eng, rows, k = self._hip, self.eng, self.rows, self.k
-        OS.spec_draft(self.hist, self.hlen, k, self.max_seq, self.tokens, self.pos, self.ngram, self.script,
-                      self.matched, self.done, self.match_ctr)
+        if self.draft is not None:
+            self._draft_model()
+        else:
+            OS.spec_draft(self.hist, self.hlen, k, self.max_seq, self.tokens, self.pos, self.ngram, self.script,
+                          self.matched, self.done, self.match_ctr)
         h = eng.buf_h[:rows]
         hip.embed(self.tokens, eng.embed_w, h)
         eng._forward_hip(h, self.slot, self.pos, None, rows, nsplit=eng.decode_nsplit(rows))
@@ -230,6 +308,28 @@ class SpecDecodeGraph(_SpecState):
         hip.argmax_finalize(self.keys, rows, self.cand, None)  # pos=None: positions are the draft kernel's
         OS.spec_accept(self.hist, self.hlen, self.limit, self.done, self.eos, self.tokens, self.cand, k, self.max_seq,
                        self.n_acc, self.acc_history, self.step_ctr)
+
+    def _draft_model(self) -> None:
+        """``dm_begin -> [draft embed -> layers -> head -> argmax_finalize -> dm_chain] x k``: the
+        target's ``tokens`` / ``pos`` filled from the draft engine's greedy continuation."""
+        hip, d, n, k = self._hip, self.draft, self.n_seq, self.k
+        OS.spec_dm_begin(self.hist, self.hlen, self.slots_t, k, self.max_seq, d.max_seq, self.d_tokens, self.d_pos,
+                         self.d_slot, self.tokens, self.pos, self.matched, self.done, self.match_ctr)
+        for j in range(k):
+            rows = 2 * n if j == 0 else n
+            with d.use_scratch(self.DRAFT_SCRATCH[min(j, 1)]):
+                h = d.buf_h[:rows]
+                if j == 0:
+                    hip.embed(self.d_tokens, d.embed_w, h)
+                    d._forward_hip(h, self.d_slot, self.d_pos, None, rows, nsplit=d.decode_nsplit(rows))
+                    d.head_gemv(h, n, self.d_keys, a_rows=self.d_last)
+                else:
+                    hip.embed(self.d_tokens1, d.embed_w, h)
+                    d._forward_hip(h, self.slots_t, self.d_pos1, None, rows, nsplit=d.decode_nsplit(rows))
+                    d.head_gemv(h, n, self.d_keys)
+            hip.argmax_finalize(self.d_keys, n, self.d_amax, None)  # greedy, no position increment
+            OS.spec_dm_chain(self.d_amax, self.hlen, self.hist.stride(0), k, j, self.max_seq, d.max_seq, self.tokens,
+                             self.d_tokens1, self.d_pos1)
 
     _STATE = ("hist", "hlen", "limit", "done", "n_acc", "matched", "match_ctr")
 
@@ -252,6 +352,8 @@ class SpecDecodeGraph(_SpecState):
         for a, v in saved.items():
             getattr(self, a).copy_(v)
         self.keys.zero_()
+        if self.draft is not None:
+            self.d_keys.zero_()
         self.step_ctr.zero_()
         if self.acc_history is not None:
             self.acc_history.zero_()
@@ -265,11 +367,14 @@ class EagerSpecDecode(_SpecState):
     """:class:`SpecDecodeGraph`'s interface without a graph: the numpy references around
     ``eng.embed`` / ``eng.forward`` / ``eng.head`` (``Sampler.sample`` with ``positions = pos + 1``
     for sampled sequences). CPU engines run this; on a GPU engine it issues the same forward and
-    head launches as the graph and serves as its twin in tests."""
+    head launches as the graph and serves as its twin in tests. ``draft=``: as for the graph;
+    ``ops.speculative.draft_model_reference`` around the draft engine's ``embed / forward / head``
+    (``ngram`` is ignored then)."""
 
     def __init__(self, eng: StageEngine, n_seq: int, k: int, slots: Optional[list] = None, ngram=(1, 3),
-                 script: bool = False, sampling: bool = False, history_len: int = 0, eos_ids=()):
-        super().__init__(eng, n_seq, k, slots, ngram, script, sampling, history_len, eos_ids)
+                 script: bool = False, sampling: bool = False, history_len: int = 0, eos_ids=(),
+                 draft: Optional[StageEngine] = None):
+        super().__init__(eng, n_seq, k, slots, ngram, script, sampling, history_len, eos_ids, draft)
         n, park = self.n_seq, self.max_seq - self.k
         self.hist = np.zeros((n, self.ld), dtype=np.int32)
         self.hlen, self.limit = np.full(n, park, dtype=np.int32), np.full(n, park, dtype=np.int32)
@@ -295,10 +400,21 @@ class EagerSpecDecode(_SpecState):
     def capture(self, warmup: bool = True) -> "EagerSpecDecode":
         return self
 
+    def _draft_rows(self, tokens, pos, slot, out_rows) -> np.ndarray:
+        """One draft iteration: the draft engine's greedy token of every row of ``out_rows``."""
+        d = self.draft
+        h = d.forward(d.embed(torch.from_numpy(tokens)), slot.tolist(), pos.tolist())
+        return d.head(h, [int(r) for r in out_rows]).cpu().numpy().astype(np.int32)
+
     def replay(self) -> None:
         eng, k = self.eng, self.k
-        self.tokens, self.pos, self.matched = OS.draft_reference(
-            self.hist, self.hlen, k, self.max_seq, self.ngram, self.script, self.done, self.match_ctr)
+        if self.draft is not None:
+            self.tokens, self.pos, self.matched, _ = OS.draft_model_reference(
+                self.hist, self.hlen, k, self.max_seq, self.draft.max_seq, self._draft_rows, self.slots, self.done,
+                self.match_ctr)
+        else:
+            self.tokens, self.pos, self.matched = OS.draft_reference(
+                self.hist, self.hlen, k, self.max_seq, self.ngram, self.script, self.done, self.match_ctr)
         h = eng.embed(torch.from_numpy(self.tokens))
         h = eng.forward(h, self.slot_rows, self.pos.tolist())
         if self.sampling:
@@ -312,12 +428,16 @@ class EagerSpecDecode(_SpecState):
 
 
 def generate_speculative(eng: StageEngine, prompts: Sequence[Sequence[int]], max_new_tokens: int, k: int = 3,
-                         sampling=None, eos_ids=None, ngram=(1, 3), script=None) -> tuple:
+                         sampling=None, eos_ids=None, ngram=(1, 3), script=None,
+                         draft: Optional[StageEngine] = None) -> tuple:
     """Prefill ``prompts`` (up to their last token) into slots ``0 .. n - 1`` of ``eng`` and decode
     speculatively - the first step feeds the last prompt token - until every sequence has
     ``max_new_tokens`` tokens or has produced an id of ``eos_ids`` (None: no stop ids).
     ``sampling``: None, one :class:`SamplingParams` or one per prompt. ``script``: one token list
-    per prompt, indexed by absolute position - drafts come from it instead of the lookup. The
+    per prompt, indexed by absolute position - drafts come from it instead of the lookup.
+    ``draft``: a draft engine (:class:`SpecDecodeGraph`) - drafts come from its greedy continuation,
+    ``ngram`` is ignored, ``matched_fraction`` is 1 and a ``script`` beside it is refused; its slots
+    ``0 .. n - 1`` are prefilled here. The
     default ``k = 3`` is the largest measured ``k`` whose step stays within 3 % of the 1-row step at
     contexts 128 and 2048 (profiles/speculative.md).
 
@@ -335,7 +455,7 @@ def generate_speculative(eng: StageEngine, prompts: Sequence[Sequence[int]], max
     sampled = any(not p.greedy for p in params)
     cls = SpecDecodeGraph if eng.gpu else EagerSpecDecode
     g = cls(eng, n, k, ngram=ngram, script=script is not None, sampling=sampled, history_len=max(1, new),
-            eos_ids=eos_ids or ())
+            eos_ids=eos_ids or (), draft=draft)
     prompts = [[int(t) for t in p] for p in prompts]
     if any(len(p) < 1 for p in prompts):
         raise ValueError("generate_speculative: an empty prompt")
