@@ -54,19 +54,18 @@
 // (its size is read off the 'last row' bits of accept) is staged into LDS and walked there; a larger
 // one is walked from global memory (L2), 1.7 x slower. lsa_grammar_mask_alt is the same kernel with
 // the other threshold that was measured.
-#include "row_scan.h"
+#include "mask_row.h"
 
 namespace {
 
-constexpr int GM_THREADS = 1024;
-constexpr int GM_WAVES = GM_THREADS / LSA_WAVE;
+constexpr int GM_THREADS = MR_THREADS;
+constexpr int GM_WAVES = MR_WAVES;
 constexpr int GM_LDS_STATES = 256;        // 128 KiB of the CU's 160 KiB: one workgroup per CU
 constexpr int GM_ALT_LDS_STATES = 128;    // 64 KiB: no faster (registers, not LDS, keep a second workgroup off the CU)
-constexpr int GM_CHUNK = 512;             // positions per wave and trip: 64 vectors of 8
-constexpr int GM_REG_WORDS = 8;           // the allow bits of 32 chunks per lane
-constexpr int GM_MAX_CHUNKS = GM_REG_WORDS * 4;
-constexpr int GM_MAX_V = GM_MAX_CHUNKS * GM_WAVES * GM_CHUNK - 8;
-constexpr int GM_EOS_MAX = 8;
+constexpr int GM_CHUNK = MR_CHUNK;        // positions per wave and trip (mask_row.h)
+constexpr int GM_REG_WORDS = MR_REG_WORDS;
+constexpr int GM_MAX_V = MR_MAX_V;
+constexpr int GM_EOS_MAX = MR_EOS_MAX;
 
 long long g_grammar_mask_calls = 0;
 
@@ -154,55 +153,18 @@ LSA_DEVICE void gm_row(bf16_raw* __restrict__ row, int V, const short* tab, int 
       for (int i = 0; i < 8; ++i) more |= pos + 4 < len[i] && st[i] >= 0;
       if (!more) break;
     }
-    unsigned mine = 0u;
+    bool alive[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const unsigned long long m = __ballot(st[i] >= 0);
-      cnt += __popcll(m);
-      if ((lane >> 3) == i) mine = (unsigned)(m >> ((lane & 7) * 8)) & 0xffu;
-    }
-#pragma unroll
-    for (int k = GM_REG_WORDS - 1; k > 0; --k) reg[k] = (reg[k] << 8) | (reg[k - 1] >> 24);
-    reg[0] = (reg[0] << 8) | mine;
+    for (int i = 0; i < 8; ++i) alive[i] = st[i] >= 0;
+    cnt += mr_push(reg, alive, lane);
   }
-  if (lane == 0) sh_cnt[wave] = cnt;
-  __syncthreads();
-  int n = 0;
-#pragma unroll
-  for (int w = 0; w < GM_WAVES; ++w) n += sh_cnt[w];
+  const int n = mr_total(cnt, sh_cnt, wave, lane);
   if (n == 0) {                                // 3. a stuck state: the row stays as it is
     if (tid == 0) *gfault_s |= 2;
     return;
   }
 
-  // 3. the stores, newest chunk first
-  const int last = nchunk - 1 - ((nchunk - 1 - wave) % GM_WAVES + GM_WAVES) % GM_WAVES;  // the wave's last chunk
-  for (int c = last; c >= wave; c -= GM_WAVES) {
-    const unsigned bits = reg[0] & 0xffu;
-#pragma unroll
-    for (int k = 0; k < GM_REG_WORDS - 1; ++k) reg[k] = (reg[k] >> 8) | (reg[k + 1] << 24);
-    reg[GM_REG_WORDS - 1] >>= 8;
-    const int v0 = c * GM_CHUNK + lane * 8 - pad;
-    if (v0 >= V || v0 + 8 <= 0 || bits == 0xffu) continue;
-    if (v0 >= 0 && v0 + 8 <= V) {
-      u32x4_t lv = ld16(row + v0);
-      bool ch = false;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned l0 = lv[j] & 0xffffu, l1 = lv[j] >> 16;
-        if (!(bits >> (2 * j) & 1u) && l0 != BF16_NEG_INF) { l0 = BF16_NEG_INF; ch = true; }
-        if (!(bits >> (2 * j + 1) & 1u) && l1 != BF16_NEG_INF) { l1 = BF16_NEG_INF; ch = true; }
-        lv[j] = l0 | (l1 << 16);
-      }
-      if (ch) st16(row + v0, lv);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int v = v0 + j;
-        if (v >= 0 && v < V && !(bits >> j & 1u) && row[v] != (bf16_raw)BF16_NEG_INF) row[v] = (bf16_raw)BF16_NEG_INF;
-      }
-    }
-  }
+  mr_store(row, V, pad, nchunk, reg, wave, lane);   // 3. the stores, newest chunk first
 }
 
 template <int LS>

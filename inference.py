@@ -91,6 +91,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--choice", action="append", default=[], metavar="TEXT",
                     help="the output is exactly one of the given texts (tokenised without special tokens), then EOS; "
                          "repeatable")
+    ap.add_argument("--json", action="store_true",
+                    help="the output is one JSON object (RFC 8259, whitespace runs of at most 2 bytes, nesting up to "
+                         "64), then EOS: a byte-level pushdown automaton masked on the device; not with --regex")
     ap.add_argument("--regex", default=None, metavar="PATTERN",
                     help="the output, as bytes, fully matches PATTERN (a byte-level DFA walked over the vocabulary's "
                          "byte strings on the device), then EOS")
@@ -157,6 +160,9 @@ def speculative_from_args(a, sp):
                          "--choice (the constraint state is sequential per token)")
     if a.regex is not None:
         raise SystemExit("[ERROR] --speculative does not combine with --regex (the DFA state is sequential per token)")
+    if a.json:
+        raise SystemExit("[ERROR] --speculative does not combine with --json (the automaton's state and stack are "
+                         "sequential per token)")
     return a.speculative, (nmin, nmax)
 
 
@@ -170,7 +176,7 @@ def sampling_from_args(a, choices=None):
     from llm_sharding_amd.runtime.sampling import SamplingParams
     pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
     if (a.temperature == 0.0 and a.top_k == 0 and a.top_p == 1.0 and a.seed is None and pen == (1.0, 0.0, 0.0)
-            and a.logprobs is None and not constraint_flags(a) and a.regex is None):
+            and a.logprobs is None and not constraint_flags(a) and a.regex is None and not a.json):
         return None
     bias = {}
     for item in a.logit_bias:
@@ -182,9 +188,9 @@ def sampling_from_args(a, choices=None):
     try:
         sp = SamplingParams(a.temperature, a.top_k, a.top_p, a.seed, *pen, logprobs=a.logprobs, logit_bias=bias or None,
                             banned_token_ids=a.ban or None, min_tokens=a.min_tokens, min_p=a.min_p, choices=choices,
-                            regex=a.regex)
+                            regex=a.regex, json_object=a.json)
     except ValueError as e:
-        if constraint_flags(a) or a.regex is not None:
+        if constraint_flags(a) or a.regex is not None or a.json:
             raise SystemExit(f"[ERROR] {e}")
         raise
     return None if sp.plain else sp
@@ -207,9 +213,9 @@ def main(argv=None):
     spec = speculative_from_args(a, sp)
     if sp is not None and a.hf_compare:
         raise SystemExit("[ERROR] --hf-compare checks the greedy decode: drop the sampling and penalty flags")
-    if (constraint_flags(a) or a.regex is not None) and (a.score or a.hf_compare):
+    if (constraint_flags(a) or a.regex is not None or a.json) and (a.score or a.hf_compare):
         raise SystemExit("[ERROR] --score and --hf-compare do not combine with --logit-bias, --ban, --min-tokens, "
-                         "--min-p, --choice or --regex")
+                         "--min-p, --choice, --regex or --json")
     if a.shards:
         cfg = LlamaConfig.from_pretrained(a.shards)
         src, tok = ShardFolderSource(a.shards, cfg), load_tokenizer(a.shards)
@@ -250,6 +256,8 @@ def main(argv=None):
         out = report(a, cfg, tok, ids, out, dt_s)
         if sp.grammar is not None:
             report_regex(sp, tok, cfg, out)
+        if sp.json_object:
+            report_json(tok, cfg, out)
         if lp:
             print_logprobs(tok, out, lp)
         return out
@@ -340,16 +348,32 @@ def report_regex(sp, tok, cfg, out: list) -> None:
           ("is a prefix of a match (cut by --max-new-tokens)" if sp.grammar.walk(data) >= 0 else "DOES NOT MATCH")))
 
 
+def report_json(tok, cfg, out: list) -> None:
+    """--json: the generated bytes and whether they parse (an output cut by --max-new-tokens is a
+    live prefix of a JSON object)."""
+    import json
+    from llm_sharding_amd.ops.grammar import VocabBytes
+    from llm_sharding_amd.ops.pda import BytePDA
+    data = VocabBytes.from_tokenizer(tok, cfg.vocab_size).decode([t for t in out if t not in cfg.eos_ids])
+    try:
+        parsed = isinstance(json.loads(data.decode("utf-8")), dict)
+    except ValueError:
+        parsed = False
+    print(f"[INFO] json: output {data!r} " + ("parses as a JSON object" if parsed else
+          ("is a live prefix of a JSON object (cut by --max-new-tokens)" if BytePDA.json().alive(data) else "DOES NOT PARSE")))
+
+
 def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out=None, tok=None) -> tuple:
     """Sampled continuation of the prefilled sequence in slot 0 (``h``: the prefill's final
     hidden): the first token from ``Sampler.sample``, the rest from a captured
     ``SamplingDecodeGraph`` on the GPU (the eager twin on the CPU). With a penalty the
     sequence's token statistics (``PenaltyState``, ``prompt_ids`` marked) ride along, with a
-    constraint its ``ConstraintState``, with a regex its ``GrammarState`` over the byte strings of
+    constraint its ``ConstraintState``, with a regex or ``json_object`` its ``GrammarState`` over the byte strings of
     ``tok``'s vocabulary (``runtime.logit_stages``). With ``sp.logprobs`` the tokens'
     log-probabilities, ranks and alternatives go into the dict ``lp_out`` (``lp``, ``rank``, ``top``:
     per token a list of (id, logprob))."""
     from llm_sharding_amd.ops.grammar import VocabBytes
+    from llm_sharding_amd.ops.pda import BytePDA
     from llm_sharding_amd.runtime.logit_stages import STAGE_CLASSES
     from llm_sharding_amd.runtime.sampling import EagerSamplingDecode, Sampler, SamplingDecodeGraph
     print(f"[INFO] sampling: temperature {sp.temperature} top_k {sp.top_k} top_p {sp.top_p} seed {sp.seed}")
@@ -359,9 +383,11 @@ def sample_tokens(eng, h, n_prompt: int, n_new: int, sp, prompt_ids=None, lp_out
         "constraints": lambda cls: (cls(eng, 1, state_rows=max(1, sum(len(c) for c in sp.choices or ()) + 2)),
                                     f"constraints: {len(sp.bias_entries())} bias entries, min_tokens {sp.min_tokens}, "
                                     f"min_p {sp.min_p}, {len(sp.choices or ())} choices"),
-        "grammar": lambda cls: (cls(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size),
-                                    dfa_rows=sp.grammar.n_states),
-                                f"regex {sp.regex!r}: a byte-level DFA of {sp.grammar.n_states} states"),
+        "grammar": lambda cls: (
+            (cls(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size), dfa_rows=1, pda=BytePDA.json()),
+             f"json: a byte-level pushdown automaton of {BytePDA.json().n_states} states") if sp.json_object else
+            (cls(eng, 1, VocabBytes.from_tokenizer(tok, eng.cfg.vocab_size), dfa_rows=sp.grammar.n_states),
+             f"regex {sp.regex!r}: a byte-level DFA of {sp.grammar.n_states} states")),
     }
     kw = {}
     for cls in STAGE_CLASSES:

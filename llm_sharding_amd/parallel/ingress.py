@@ -128,7 +128,9 @@ def submit_message(srv, msg: dict, tokenizer, default_new: int, replies: Replies
     invalid or the automaton does not fit the server's arena; optional ``regex``: the output's bytes
     fully match the pattern (``ops.grammar``), refused with an error reply on a syntax error, a
     server without ``vocab_bytes``, a DFA that does not fit its arena or a state that allows no
-    token; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
+    token; optional ``json_object: true`` or ``response_format: {"type": "json_object"}``: the
+    output is one JSON object (``ops.pda``), refused with an error reply together with ``regex`` or
+    where the server cannot serve it; optional ``cache_prefix``: the leading tokens worth keeping in the server's prefix pool;
     optional ``n > 1``: that many samples of each prompt sharing one prefill, answered with a
     ``"choices"`` list - needs a server with ``prefix_slots``). Returns the number of requests
     queued."""

@@ -163,8 +163,11 @@ class PipelineServer:
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
                  ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
                  prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256,
-                 vocab_bytes=None, dfa_rows: int = 4096, kv_dtype: str = "bf16"):
+                 vocab_bytes=None, dfa_rows: int = 4096, kv_dtype: str = "bf16", json_max_ws: int = 2):
         self.cfg, self.rank, self.world = cfg, rank, world
+        if isinstance(json_max_ws, bool) or not isinstance(json_max_ws, int) or not 0 <= json_max_ws <= 8:
+            raise ValueError(f"json_max_ws must be an integer in [0, 8], got {json_max_ws!r}")
+        self.json_max_ws = json_max_ws
         from ..runtime.engine_kv8 import check_kv_dtype
         check_kv_dtype(kv_dtype)
         if kv_dtype == "fp8" and int(prefix_slots) > 0:
@@ -212,9 +215,11 @@ class PipelineServer:
         # logit stages (runtime.logit_stages): each one's tables exist, and the graphs carry its
         # launch, from the first request that asks for it on - the penalties' token statistics, the
         # constraints' automaton arena (state_rows rows), the DFA arena of a regex (dfa_rows rows of
-        # 512 B; vocab_bytes, an ops.grammar.VocabBytes, is what such requests need). The host
+        # 512 B; vocab_bytes, an ops.grammar.VocabBytes, is what such requests need; the same stage
+        # serves json_object requests with the automaton BytePDA.json(max_ws=json_max_ws)). The host
         # allocators of the two arenas exist from the first such submit on.
         self.penalties = self.constraints = self.grammar = None
+        self._json = None  # (BytePDA or None, the vocabulary check's error or None), from the first use on
         self.state_rows, self.vocab_bytes, self.dfa_rows = int(state_rows), vocab_bytes, int(dfa_rows)
         self._arena = self._garena = self._gcheck = None
         # logprobs: the graphs carry the lsa_logprobs launch from the first request that asks on
@@ -302,8 +307,26 @@ class PipelineServer:
             "constraints": lambda: LS.ConstraintState(self.eng, n, self.state_rows,
                                                       allocator=self._allocator("_arena", self.state_rows)),
             "grammar": lambda: LS.GrammarState(self.eng, n, self.vocab_bytes, self.dfa_rows,
-                                               allocator=self._allocator("_garena", self.dfa_rows)),
+                                               allocator=self._allocator("_garena", self.dfa_rows),
+                                               pda=self._json_pda()[0]),
         }[name]()
+
+    def _json_pda(self) -> tuple:
+        """``(pda, None)``: the JSON automaton of this server, checked against its vocabulary; or
+        ``(None, error)`` when the vocabulary cannot spell JSON (or the configuration has no EOS id)
+        - then json_object requests are refused at submit and the stage serves regexes alone."""
+        from ..ops.pda import BytePDA, check_vocab
+        with self._lock:
+            if self._json is None:
+                pda = BytePDA.json(max_ws=self.json_max_ws)
+                try:
+                    if not list(self.cfg.eos_ids):
+                        raise ValueError("json_object needs an EOS id in the configuration: the output ends with it")
+                    check_vocab(pda, self.vocab_bytes, self.cfg.eos_ids)
+                    self._json = (pda, None)
+                except ValueError as e:
+                    self._json = (None, str(e))
+            return self._json
 
     def _enable_stage(self, name: str) -> None:
         """First request that asks for the logit stage ``name`` (sampling already on): allocate its
@@ -630,8 +653,9 @@ class PipelineServer:
         when they do not fit), and ``regex`` (compiled when the parameters were built; here its
         DFA is checked against the server's ``vocab_bytes`` and its rows of the DFA arena are
         reserved - ValueError without ``vocab_bytes``, when the DFA does not fit, or when one of its
-        states allows no token of the vocabulary) (None, or temperature 0 with every penalty off, no logprobs and no
-        constraint: greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
+        states allows no token of the vocabulary), and ``json_object`` (ValueError when the
+        configuration has no EOS id, without ``vocab_bytes``, or when the vocabulary cannot spell JSON)
+        (None, or temperature 0 with every penalty off, no logprobs and no constraint: greedy); its output depends only on its own prompt, seed and penalties, not on the slot or
         batch it runs in. With ``logprobs`` the finished :class:`Request` holds ``token_logprobs``,
         ``ranks`` and (``logprobs >= 1``) ``top_logprobs``, one entry per generated token."""
         if not self.first:
@@ -657,9 +681,12 @@ class PipelineServer:
                 with self._lock:
                     arena.acquire(constraint.automaton)
         grammar = None if sampling is None else sampling.grammar
-        if grammar is not None:
+        if grammar is not None or (sampling is not None and sampling.json_object):
             try:
-                self._reserve_grammar(grammar)
+                if grammar is not None:
+                    self._reserve_grammar(grammar)
+                else:
+                    self._check_json()
             except ValueError:
                 if constraint is not None and constraint.automaton is not None:
                     self._arena.release(constraint.automaton.digest)
@@ -675,6 +702,20 @@ class PipelineServer:
                     grammar=grammar)
         self.incoming.put(r)
         return rid
+
+    def _check_json(self) -> None:
+        """A json_object request is submitted: ValueError unless this server can serve it."""
+        from ..runtime.sampling import _check_full_head
+        if self.vocab_bytes is None:
+            raise ValueError("json_object needs the byte strings of the vocabulary: build the server with "
+                             "vocab_bytes=ops.grammar.VocabBytes.from_tokenizer(...)")
+        if self.vocab_bytes.V != self.cfg.vocab_size:
+            raise ValueError(f"vocab_bytes covers {self.vocab_bytes.V} tokens, the configuration has "
+                             f"{self.cfg.vocab_size}")
+        _check_full_head(self.eng)
+        err = self._json_pda()[1]
+        if err is not None:
+            raise ValueError(err)
 
     def _reserve_grammar(self, dfa) -> None:
         """A request with a regex is submitted: check its DFA against the vocabulary's bytes and

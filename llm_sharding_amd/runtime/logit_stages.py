@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -21,6 +22,7 @@ import torch
 
 from ..ops import constraints as K
 from ..ops import grammar as G
+from ..ops import pda as J
 from ..ops import penalties as P
 from .engine import StageEngine
 
@@ -334,13 +336,21 @@ class GrammarState(ArenaStage):
     :class:`ArenaStage`.
     In a step ``lsa_grammar_mask`` advances the rows' DFA states by the bytes of the input tokens
     and masks every token whose bytes die in the automaton; rows whose slots hold no regex are
-    skipped."""
-    name, request, tables = "grammar", "a request with a regex", "the grammar tables"
+    skipped.
+
+    ``pda`` (an :class:`ops.pda.BytePDA`, in practice ``BytePDA.json()``): the stage also serves
+    ``json_object`` requests. It then owns the automaton's planes ``ptab`` / ``paccept`` and the
+    per-slot configuration ``jstate / jdepth / jstack`` (16 B per slot), and its step launches
+    ``lsa_pda_mask`` after ``lsa_grammar_mask``: a slot holds a regex or JSON, never both, and each
+    kernel skips the other's slots. The vocabulary is checked against the automaton here
+    (``ops.pda.check_vocab``: ValueError), so an admitted request never meets a row without a
+    column. Without ``pda`` the stage allocates and launches exactly what it does for a regex."""
+    name, request, tables = "grammar", "a request with a regex or json_object", "the grammar tables"
     DISTURBED, ROWS_ARG = ("gstate", "gfault"), "dfa_rows"
-    wants = staticmethod(lambda params: params.grammar is not None)
+    wants = staticmethod(lambda params: params.grammar is not None or params.json_object)
 
     def __init__(self, eng: StageEngine, n_slots: int, vocab: "G.VocabBytes", dfa_rows: int = 4096,
-                 allocator: Optional[K.ArenaAllocator] = None):
+                 allocator: Optional[K.ArenaAllocator] = None, pda: Optional["J.BytePDA"] = None):
         _check_full_head(eng)
         if not isinstance(vocab, G.VocabBytes) or vocab.V != eng.cfg.vocab_size:
             raise ValueError(f"GrammarState: a VocabBytes over the configuration's {eng.cfg.vocab_size} tokens, got "
@@ -355,6 +365,17 @@ class GrammarState(ArenaStage):
         self.gbase = torch.zeros(n, dtype=torch.int32, device=dev)
         self.gfault = torch.zeros(n, dtype=torch.int32, device=dev)
         self.checked = check_vocab_cache(vocab, self.eos_ids)
+        self.pda = pda
+        if pda is not None:
+            if not isinstance(pda, J.BytePDA):
+                raise ValueError(f"GrammarState: pda must be an ops.pda.BytePDA, got {type(pda).__name__}")
+            J.check_vocab(pda, vocab, self.eos_ids)
+            self.ptab = torch.from_numpy(np.array(pda.next)).to(dev)
+            self.paccept = torch.from_numpy(np.array(pda.accept)).to(dev)
+            self.jstate = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self.jdepth = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.jstack = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.DISTURBED = ("gstate", "gfault", "jstate", "jdepth", "jstack")
 
     def check(self, dfa: "G.ByteDFA") -> None:
         """ValueError unless every state of ``dfa`` allows at least one token of this vocabulary."""
@@ -375,6 +396,15 @@ class GrammarState(ArenaStage):
         self.release(slot)
         dfa = None if params is None else params.grammar
         if dfa is None:
+            if params is not None and params.json_object:
+                if self.pda is None:
+                    raise ValueError("json_object needs a GrammarState built with pda=BytePDA.json()")
+                if not self.eos_ids:
+                    raise ValueError("json_object needs an EOS id in the configuration: the output ends with it")
+                self.jdepth[slot] = 0
+                self.jstack[slot] = 0
+                self.jstate[slot] = 0
+                self.gfault[slot] = 0
             return
         if not acquired:
             self.check(dfa)
@@ -391,18 +421,29 @@ class GrammarState(ArenaStage):
         next :meth:`admit`)."""
         self._drop(slot)
         self.gstate[slot] = -1
+        if self.pda is not None:
+            self.jstate[slot] = -1
 
     def leave(self, slot: int, params) -> Optional[str]:
         fault = int(self.gfault[slot])
         self.release(slot)
-        return (f"grammar fault {fault} under regex {params.regex!r} (1: a token outside the pattern was fed, 2: a "
+        what = "json_object" if params.grammar is None else f"regex {params.regex!r}"
+        return (f"grammar fault {fault} under {what} (1: a token outside the pattern was fed, 2: a "
                 "state allowed no token)") if fault else None
 
     def _reference(self, logits, V, slots, tokens_in, _):
-        return G.grammar_mask_reference(logits, V, self, slots, tokens_in)
+        out, gstate, gfault = G.grammar_mask_reference(logits, V, self, slots, tokens_in)
+        if self.pda is None:
+            return out, gstate, gfault
+        tb = SimpleNamespace(**{k: getattr(self, k) for k in J.TABLES})
+        tb.gfault = gfault
+        out, jstate, jdepth, jstack, gfault = J.pda_mask_reference(out, V, tb, slots, tokens_in)
+        return out, gstate, gfault, jstate, jdepth, jstack
 
     def _kernel(self, logits, n, slot, tokens, rows, pos, ctr_add) -> None:
         G.grammar_mask(logits, self.eng.cfg.vocab_size, n, slot, tokens, self)
+        if self.pda is not None:
+            J.pda_mask(logits, self.eng.cfg.vocab_size, n, slot, tokens, self)
 
 
 def check_vocab_cache(vocab: "G.VocabBytes", eos_ids):

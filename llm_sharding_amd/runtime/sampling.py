@@ -71,7 +71,13 @@ class SamplingParams:
     into a byte-level DFA (:attr:`grammar`), so a syntax error surfaces at construction. It excludes
     ``allowed_token_ids``, ``choices``, ``automaton``, ``banned_token_ids``, a ``-inf`` bias and
     ``min_tokens`` for the same reason; a finite ``logit_bias``, ``min_p``, the penalties, top-k /
-    top-p and ``logprobs`` combine with it."""
+    top-p and ``logprobs`` combine with it.
+
+    ``json_object`` (``ops.pda``): the output, as bytes, is one JSON object (RFC 8259, whitespace
+    runs bounded by the server's ``json_max_ws``, nesting up to 64), then EOS - OpenAI's
+    ``response_format: {"type": "json_object"}``. It excludes ``regex`` and what ``regex``
+    excludes, for the same reason, and combines with what ``regex`` combines with; at temperature 0
+    the request still takes the sampling path (the arg-max of the masked logits)."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
@@ -88,10 +94,23 @@ class SamplingParams:
     choices: Optional[list] = None
     automaton: Optional[Any] = None
     regex: Optional[str] = None
+    json_object: bool = False
 
     def __post_init__(self):
         self._check_constraints()
         self._grammar = None
+        if not isinstance(self.json_object, bool):
+            raise ValueError(f"json_object must be a bool, got {self.json_object!r}")
+        if self.json_object:
+            clash = [k for k in ("regex", "allowed_token_ids", "choices", "automaton", "banned_token_ids")
+                     if getattr(self, k) is not None]
+            if self.min_tokens:
+                clash.append("min_tokens")
+            if any(b == float("-inf") for _, b in self.bias_entries()) and "banned_token_ids" not in clash:
+                clash.append("a -inf bias")
+            if clash:
+                raise ValueError(f"json_object cannot be combined with {' / '.join(clash)}: the JSON grammar decides "
+                                 "what may appear and when the output ends")
         if self.regex is not None:
             if not isinstance(self.regex, str):
                 raise ValueError(f"regex must be a str, got {self.regex!r}")
@@ -220,9 +239,9 @@ class SamplingParams:
     @property
     def plain(self) -> bool:
         """Needs no sampling path at all: temperature 0, every penalty off, no logprobs, no
-        constraint, no regex."""
+        constraint, no regex, no json_object."""
         return (self.greedy and not self.penalized and self.logprobs is None and not self.constrained
-                and self._grammar is None)
+                and self._grammar is None and not self.json_object)
 
     @property
     def n_top(self) -> int:
@@ -233,14 +252,23 @@ class SamplingParams:
     def from_dict(cls, d: dict) -> Optional["SamplingParams"]:
         """``temperature / top_k / top_p / seed / repetition_penalty / presence_penalty /
         frequency_penalty / logprobs / logit_bias / banned_token_ids / min_tokens / min_p /
-        allowed_token_ids / choices / regex`` keys of a request dict (``logit_bias`` with string or integer
-        keys); None (greedy) when none of them is present."""
+        allowed_token_ids / choices / regex / json_object`` keys of a request dict (``logit_bias`` with string or
+        integer keys), and ``response_format: {"type": "json_object"}`` (``"text"``: nothing; any
+        other type: ValueError); None (greedy) when none of them is present."""
         keys = ("temperature", "top_k", "top_p", "seed", "repetition_penalty", "presence_penalty", "frequency_penalty",
                 "logprobs", "logit_bias", "banned_token_ids", "min_tokens", "min_p", "allowed_token_ids", "choices",
-                "regex")
-        if not any(d.get(k) is not None for k in keys):
+                "regex", "json_object")
+        kw = {k: d[k] for k in keys if d.get(k) is not None and not (k == "json_object" and d[k] is False)}
+        fmt = d.get("response_format")
+        if fmt is not None:
+            kind = fmt.get("type") if isinstance(fmt, dict) else None
+            if kind == "json_object":
+                kw["json_object"] = True
+            elif kind != "text":
+                raise ValueError(f"response_format: {{'type': 'json_object'}} or {{'type': 'text'}}, got {fmt!r}")
+        if not kw:
             return None
-        return cls(**{k: d[k] for k in keys if d.get(k) is not None})
+        return cls(**kw)
 
 
 _REGEX_CACHE: dict = {}

@@ -168,6 +168,9 @@ class _SpecState:
         if p.grammar is not None:
             raise ValueError("speculative: a regex keeps sequential state per slot (the DFA state after every token) "
                              "and is not supported together with speculation")
+        if p.json_object:
+            raise ValueError("speculative: json_object keeps sequential state per slot (the automaton's state and "
+                             "stack after every token) and is not supported together with speculation")
         if not p.greedy and not self.sampling:
             raise ValueError("speculative: a sampled sequence needs sampling=True")
         row = np.zeros(self.ld, dtype=np.int32)

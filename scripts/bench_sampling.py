@@ -41,8 +41,18 @@
    ``SamplingDecodeGraph`` without ``grammar=``, with it and no regex row, and with every row
    under the permissive and the tight pattern.
 
+7. ``--json`` (results: profiles/json_mask.md, written by the run) instead: ``lsa_pda_mask`` (JSON mode, the
+   byte-level pushdown automaton ``BytePDA.json()``) alone at 1 and 512 rows of V = 32000 over the same
+   synthetic vocabulary, 50 launches captured in one graph, every row at the start of the text
+   (only ``{`` and whitespace survive) and inside a string (nearly every token walks to its end),
+   in alternating windows with ``lsa_grammar_mask`` under the permissive pattern ``[ -~]*`` and with
+   the same automaton padded past the LDS threshold (the L2 path); and the TPOT of a 7B-shaped
+   ``SamplingDecodeGraph`` without ``grammar=``, with a ``GrammarState(pda=...)`` and no JSON row, and
+   with every row inside a JSON string.
+
     python scripts/bench_sampling.py [--layers 32] [--skip-kernel] [--skip-tpot] [--json-out FILE]
     python scripts/bench_sampling.py --grammar [--layers 32] [--json-out FILE] [--md-out profiles/grammar_mask.md]
+    python scripts/bench_sampling.py --json [--layers 32] [--json-out FILE] [--md-out profiles/json_mask.md]
     python scripts/bench_sampling.py --penalties [--layers 32] [--json-out FILE]
     python scripts/bench_sampling.py --logprobs [--layers 32] [--json-out FILE]
     python scripts/bench_sampling.py --constraints [--layers 32] [--json-out FILE]
@@ -60,6 +70,7 @@ from llm_sharding_amd.config import LlamaConfig  # noqa: E402
 from llm_sharding_amd.ops import constraints as K  # noqa: E402
 from llm_sharding_amd.ops import grammar as G  # noqa: E402
 from llm_sharding_amd.ops import logprobs as LP  # noqa: E402
+from llm_sharding_amd.ops import pda as J  # noqa: E402
 from llm_sharding_amd.ops import penalties as P  # noqa: E402
 from llm_sharding_amd.ops import sampling as S  # noqa: E402
 from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource, StageEngine  # noqa: E402
@@ -575,6 +586,180 @@ def main_grammar(a) -> dict:
     return out
 
 
+JSON_CONFIGS = {"start": b"", "in_string": b'{"key":"'}
+
+
+def padded_pda(pda: "J.BytePDA", states: int) -> "J.BytePDA":
+    """``pda`` with unreachable dead states appended up to ``states``: the same language and the same
+    walks, a table past the LDS threshold."""
+    import numpy as np
+    nxt = np.full((3, states, 256), -1, dtype=np.int16)
+    nxt[:, :pda.n_states] = pda.next
+    acc = np.zeros(states, dtype=np.uint8)
+    acc[:pda.n_states] = pda.accept
+    return J.BytePDA(nxt, acc)
+
+
+def bench_pda_mask(rows: int, vocab, rounds: int = 5) -> list:
+    """``lsa_pda_mask`` with every row in one configuration of the JSON automaton, staged into LDS
+    and (padded) walked from L2, and ``lsa_grammar_mask`` under ``[ -~]*``, on the same logits, in
+    alternating windows of 50 captured launches; the two walks of the automaton must give the same
+    bits."""
+    from types import SimpleNamespace
+    V = vocab.V
+    g = torch.Generator(device=DEV).manual_seed(rows + V)
+    lg0 = (2.5 * torch.randn((rows, V), generator=g, device=DEV)).to(torch.bfloat16)
+    lg = lg0.clone()
+    pda = J.BytePDA.json()
+    big = padded_pda(pda, J.lds_states() + 1)
+    dfa = G.ByteDFA.from_regex("[ -~]*")
+    flags = dfa.accept.astype("uint8") * G.ACCEPT
+    flags[dfa.n_states - 1] |= G.LAST
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=DEV)  # noqa: E731
+    z = lambda dt=torch.int32: torch.zeros(rows, dtype=dt, device=DEV)  # noqa: E731
+    shared = dict(offsets=torch.from_numpy(vocab.offsets.copy()).to(DEV), data=torch.from_numpy(vocab.data.copy()).to(DEV),
+                  eos=i32([2] + [-1] * 7))
+    rx = SimpleNamespace(arena=torch.from_numpy(dfa.next.copy()).to(DEV), accept=torch.from_numpy(flags).to(DEV),
+                         gstate=z(), gbase=z(), gfault=z(), **shared)
+    slot = torch.arange(rows, dtype=torch.int32, device=DEV)
+
+    def restore():
+        lg.copy_(lg0)
+
+    out = []
+    for label, prefix in JSON_CONFIGS.items():
+        q, d, st = pda.walk(prefix)
+        tbs = {}
+        for name, p in (("lds", pda), ("l2", big)):
+            tbs[name] = SimpleNamespace(ptab=torch.from_numpy(p.next.copy()).to(DEV),
+                                        paccept=torch.from_numpy(p.accept.copy()).to(DEV),
+                                        jstate=torch.full((rows,), q, dtype=torch.int32, device=DEV),
+                                        jdepth=torch.full((rows,), d, dtype=torch.int32, device=DEV),
+                                        jstack=torch.full((rows,), st, dtype=torch.int64, device=DEV), gfault=z(), **shared)
+        fns = {"lsa_pda_mask lds": lambda: J.pda_mask(lg, V, rows, slot, None, tbs["lds"]),
+               "lsa_pda_mask l2": lambda: J.pda_mask(lg, V, rows, slot, None, tbs["l2"]),
+               "lsa_grammar_mask [ -~]*": lambda: G.grammar_mask(lg, V, rows, slot, None, rx)}
+        masks = {}
+        for name in ("lsa_pda_mask lds", "lsa_pda_mask l2"):
+            restore()
+            fns[name]()
+            masks[name] = lg.clone()
+        torch.cuda.synchronize()
+        assert torch.equal(masks["lsa_pda_mask lds"].view(torch.int16), masks["lsa_pda_mask l2"].view(torch.int16))
+        allowed = int((masks["lsa_pda_mask lds"][0] != float("-inf")).sum())
+        res = {name: [] for name in fns}
+        for _ in range(rounds):                    # alternating windows: one _steady_fresh per kernel and round
+            for name, fn in fns.items():
+                res[name].append(_steady_fresh(fn, restore))
+        for name in fns:
+            r = {k: round(statistics.median(x[k] for x in res[name]), 2) for k in ("steady_graphed_us", "fresh_graphed_us")}
+            r["fresh_spread_us"] = round(max(x["fresh_graphed_us"] for x in res[name]) - min(x["fresh_graphed_us"] for x in res[name]), 2)
+            states = dfa.n_states if "grammar" in name else (big if name.endswith("l2") else pda).n_states
+            out.append({"kernel": name, "config": label if "pda" in name else "start state", "states": states, "rows": rows,
+                        "V": V, "allowed": allowed if "pda" in name else int((dfa.step_tokens(vocab, [0])[0] >= 0).sum()),
+                        "table_KB": round(states * (1536 if "pda" in name else 512) / 1024, 1), **r})
+        assert int(tbs["lds"].gfault.sum()) == 0 and int(tbs["l2"].gfault.sum()) == 0 and int(rx.gfault.sum()) == 0
+    return out
+
+
+def bench_tpot_json(layers: int, rows: int, vocab, rounds: int = 5, steps: int = 20) -> dict:
+    cfg = LlamaConfig(num_hidden_layers=layers, vocab_size=32000, max_position_embeddings=512, name=f"7B-{layers}L")
+    eng = StageEngine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                      max_slots=rows, max_seq=128, max_prefill_rows=max(rows, 128))
+    pda = J.BytePDA.json()
+    gs = GrammarState(eng, rows, vocab, dfa_rows=64, pda=pda)
+    graphs = {"sampling": SamplingDecodeGraph(eng, rows, "full"),
+              "json_idle": SamplingDecodeGraph(eng, rows, "full", grammar=gs),
+              "json": SamplingDecodeGraph(eng, rows, "full", grammar=gs)}
+    for r in range(rows):
+        for name, g in graphs.items():
+            g.set_params(r, SamplingParams(0.7, top_p=0.9, seed=1000 + r, json_object=name == "json"))
+    for g in graphs.values():
+        g.capture()
+    tok0 = torch.randint(3, cfg.vocab_size, (rows,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(DEV)
+    q, d, st = pda.walk(JSON_CONFIGS["in_string"])
+    js = SamplingParams(0.7, top_p=0.9, seed=1000, json_object=True)
+    times = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            for r in range(rows):
+                gs.admit(r, js if name == "json" else None)
+            if name == "json":                    # every row inside a string: nearly every token walks to its end
+                gs.jstate.fill_(q)
+                gs.jdepth.fill_(d)
+                gs.jstack.fill_(st)
+            g.set_positions()
+            g.tokens.copy_(tok0 if name != "json" else torch.full_like(tok0, 3 + ord("a")))
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            times[name].append(_events(g.replay, steps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    fault = int(gs.gfault.sum())
+    del graphs, gs, eng
+    torch.cuda.empty_cache()
+    out = {"layers": layers, "rows": rows, "gfault": fault}
+    for k, v in med.items():
+        out[f"{k}_ms"] = round(v, 4)
+        out[f"{k}_spread_ms"] = round(max(times[k]) - min(times[k]), 4)
+        if k != "sampling":
+            out[f"{k}_delta_ms"] = round(v - med["sampling"], 4)
+    return out
+
+
+def json_markdown(out: dict) -> str:
+    pda = J.BytePDA.json()
+    lines = ["# lsa_pda_mask (JSON mode) on MI355X", "",
+             f"`python scripts/bench_sampling.py --json`: the automaton `BytePDA.json()` (top level an object, "
+             f"`max_ws` = 2) has {pda.n_states} states = {pda.n_states * 1536} bytes of LDS for its three planes "
+             f"(1536 B per state; the kernel stages automata of up to {J.lds_states()} states = "
+             f"{J.lds_states() * 1536} bytes, larger ones are walked from L2); `BytePDA.json(max_ws=8)` has "
+             f"{J.BytePDA.json(max_ws=8).n_states} states and takes the L2 path. {J.block_threads()} threads per row (one "
+             "workgroup). V = 32000 over the synthetic vocabulary (256 one-byte tokens plus seeded ASCII strings of 2 to 12 "
+             "bytes); 50 launches captured in one graph, all kernels in one process in alternating windows, median of 5 "
+             "rounds. steady: the masks are already in place (reads only); fresh: the logits are restored in front of every "
+             "launch and the restoring copy, captured alone, is subtracted. `start`: every row at the start of the text "
+             "(only `{` and whitespace survive, nearly every walk dies at its first byte); `in_string`: every row inside a "
+             "string (nearly every token walks to its end). `l2`: the same automaton padded with dead states to "
+             f"{J.lds_states() + 1} states, the same bits. `lsa_grammar_mask` under `[ -~]*` is the regex kernel's "
+             "every-token-walks-to-its-end case.", "",
+             "| kernel | configuration | states | table | rows | allowed | steady us | fresh us | fresh spread us |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for r in out["kernel"]:
+        lines.append(f"| {r['kernel']} | {r['config']} | {r['states']} | {r['table_KB']} KB | {r['rows']} | {r['allowed']} | "
+                     f"{r['steady_graphed_us']} | {r['fresh_graphed_us']} | {r['fresh_spread_us']} |")
+    if out["tpot"]:
+        lines += ["", "Step time of a 7B-shaped `SamplingDecodeGraph` (temperature 0.7, top-p 0.9), alternating windows of "
+                  "20 replays in one process, median of 5: without `grammar=`, with a `GrammarState(pda=...)` and no JSON row "
+                  "(both mask kernels skip every row), and with every row a JSON row that starts inside a string.", "",
+                  "| layers | rows | sampling ms | stage, no JSON row ms | JSON rows ms | spreads ms |", "|---|---|---|---|---|---|"]
+        for r in out["tpot"]:
+            lines.append(f"| {r['layers']} | {r['rows']} | {r['sampling_ms']} | {r['json_idle_ms']} ({r['json_idle_delta_ms']:+}) | "
+                         f"{r['json_ms']} ({r['json_delta_ms']:+}) | {r['sampling_spread_ms']} / {r['json_idle_spread_ms']} / "
+                         f"{r['json_spread_ms']} |")
+    return "\n".join(lines) + "\n"
+
+
+def main_json(a) -> dict:
+    out = {"kernel": [], "tpot": [], "lds_states": J.lds_states(), "threads": J.block_threads(),
+           "json_states": J.BytePDA.json().n_states}
+    vocab = synthetic_vocab()
+    for rows in (1, 512):
+        for r in bench_pda_mask(rows, vocab):
+            out["kernel"].append(r)
+            print(json.dumps(r), flush=True)
+    if not a.skip_tpot:
+        for rows in (1, 512):
+            r = bench_tpot_json(a.layers, rows, vocab)
+            out["tpot"].append(r)
+            print(json.dumps(r), flush=True)
+    md = a.md_out if a.md_out != "profiles/grammar_mask.md" else "profiles/json_mask.md"
+    os.makedirs(os.path.dirname(os.path.abspath(md)), exist_ok=True)
+    with open(md, "w") as f:
+        f.write(json_markdown(out))
+    return out
+
+
 def main_constraints(a) -> dict:
     out = {"kernel": [], "tpot": []}
     for rows in (1, 512):
@@ -630,14 +815,18 @@ def main():
                     help="measure lsa_logit_process and the step under choices instead")
     ap.add_argument("--grammar", action="store_true",
                     help="measure lsa_grammar_mask, the dense automaton beside it and the step under a regex instead")
-    ap.add_argument("--md-out", default="profiles/grammar_mask.md", help="--grammar: where its table goes")
+    ap.add_argument("--json", action="store_true",
+                    help="measure lsa_pda_mask (JSON mode), the regex kernel beside it and the step with JSON rows instead")
+    ap.add_argument("--md-out", default="profiles/grammar_mask.md",
+                    help="--grammar / --json: where the table goes (--json: profiles/json_mask.md by default)")
     ap.add_argument("--json-out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sampling.py measures on the GPU: none found")
-    special = a.penalties or a.logprobs or a.constraints or a.grammar
+    special = a.penalties or a.logprobs or a.constraints or a.grammar or a.json
     out = (main_penalties(a) if a.penalties else main_logprobs(a) if a.logprobs else
-           main_constraints(a) if a.constraints else main_grammar(a) if a.grammar else {"kernel": [], "tpot": []})
+           main_constraints(a) if a.constraints else main_grammar(a) if a.grammar else
+           main_json(a) if a.json else {"kernel": [], "tpot": []})
     for V in (() if a.skip_kernel or special else (32000, 128256)):
         for rows in (1, 128, 512):
             for mode in ("temperature", "top_k", "top_p"):

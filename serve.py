@@ -28,7 +28,10 @@ keys penalise repeated tokens on the device (also at temperature 0; one stage on
 ``banned_token_ids``, ``min_tokens``, ``min_p``, ``allowed_token_ids`` and ``choices`` keys constrain
 the output on the device (one stage only; ``--state-rows`` sizes the automaton arena); a ``regex``
 key makes the output's bytes fully match a pattern (one stage only; ``--dfa-rows`` sizes the
-byte-level DFA arena; ``--regex PATTERN`` does the same for every request of the load test);
+byte-level DFA arena; ``--regex PATTERN`` does the same for every request of the load test); a
+``json_object: true`` or ``response_format: {"type": "json_object"}`` key makes the output one JSON
+object (one stage only; ``--json`` does the same for the load test, ``--json-max-ws`` bounds the
+whitespace runs);
 ``--temperature --top-k --top-p --repetition-penalty --presence-penalty --frequency-penalty
 --logprobs --min-p --min-tokens`` do the same for the synthetic load test (request i seeded with
 ``--seed`` + i).
@@ -91,6 +94,10 @@ def main():
                          "with the first constrained request: 16 MB at V = 32000, 66 MB at V = 128256 for 256)")
     ap.add_argument("--regex", default=None, metavar="PATTERN",
                     help="load test: every request's output, as bytes, fully matches PATTERN (one stage only)")
+    ap.add_argument("--json", action="store_true",
+                    help="load test: every request's output is one JSON object (one stage only; not with --regex)")
+    ap.add_argument("--json-max-ws", type=int, default=2, metavar="N",
+                    help="json_object requests: the longest whitespace run between JSON tokens, 0..8")
     ap.add_argument("--dfa-rows", type=int, default=4096, metavar="N",
                     help="rows of the byte-level DFA arena of requests with a regex (one per DFA state, 512 B each "
                          "whatever the vocabulary; allocated with the first such request)")
@@ -165,7 +172,7 @@ def main():
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
                          streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows,
-                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows, kv_dtype=a.kv_dtype)
+                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows, kv_dtype=a.kv_dtype, json_max_ws=a.json_max_ws)
     if rank != 0:
         srv.serve()
     elif a.requests:
@@ -176,11 +183,11 @@ def main():
             pen = (a.repetition_penalty, a.presence_penalty, a.frequency_penalty)
             kw = {}
             if (a.temperature > 0 or pen != (1.0, 0.0, 0.0) or a.logprobs is not None or a.min_p is not None
-                    or a.min_tokens or a.regex is not None):
+                    or a.min_tokens or a.regex is not None or a.json):
                 from llm_sharding_amd.runtime.sampling import SamplingParams
                 kw["sampling"] = SamplingParams(a.temperature, a.top_k, a.top_p, rc.seed + i * a.n, *pen,
                                                 logprobs=a.logprobs, min_p=a.min_p, min_tokens=a.min_tokens,
-                                                regex=a.regex)
+                                                regex=a.regex, json_object=a.json)
             if a.n > 1:
                 srv.submit_n(ids, a.n, rc.max_new_tokens, eos_ids=(), **kw)
             elif shared and a.prefix_slots:
