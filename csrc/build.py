@@ -59,7 +59,10 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     # csrc/cache/: KV-cache management (fork), outside them too
     # csrc/spec/: speculative decoding's draft / accept kernels, outside them too
     # csrc/quant/: the int4 weight format's decode GEMV, which the bf16 greedy path never launches
+    # csrc/gemm_skp/: gemm_sk's split-K projections with the fix-up shared by all contributors
+    # (includes kernels/gemm_sk.hip unchanged; the engine routes to it in runtime/engine_skp.py)
     kernel_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) +
+                         glob.glob(os.path.join(CSRC, "gemm_skp", "*.hip")) +
                          glob.glob(os.path.join(CSRC, "sampling", "*.hip")) +
                          glob.glob(os.path.join(CSRC, "cache", "*.hip")) +
                          glob.glob(os.path.join(CSRC, "spec", "*.hip")) +

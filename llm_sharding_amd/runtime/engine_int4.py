@@ -258,7 +258,8 @@ def make_stage_engine(cfg, start: int, end: int, device="cpu", dtype=torch.bfloa
                       kv_dtype: str = "bf16", **kw) -> StageEngine:
     """``StageEngine`` for ``weight_dtype`` "bf16" / "fp8" (anything else raises there),
     ``Int4StageEngine`` for "int4"; ``kv_dtype="fp8"`` on a GPU: ``Fp8KVStageEngine``
-    (runtime/engine_kv8.py; bf16 or fp8 weights). A CPU engine ignores ``kv_dtype`` as it ignores
+    (runtime/engine_kv8.py; bf16 or fp8 weights); the default dtypes on a GPU: ``SkpStageEngine``
+    (runtime/engine_skp.py, StageEngine plus the gemm_skp route). A CPU engine ignores ``kv_dtype`` as it ignores
     ``weight_dtype``; a value other than "bf16" / "fp8" raises on every device."""
     from .engine_kv8 import Fp8KVStageEngine, check_kv_dtype
     check_kv_dtype(kv_dtype, weight_dtype)
@@ -266,4 +267,9 @@ def make_stage_engine(cfg, start: int, end: int, device="cpu", dtype=torch.bfloa
         return Fp8KVStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)
     if weight_dtype == "int4":
         return Int4StageEngine(cfg, start, end, device, dtype, **kw)
+    if torch.device(device).type == "cuda":
+        # the default dtypes on a GPU: StageEngine plus the gemm_skp route of the residual
+        # projections at 385..512 decode rows (runtime/engine_skp.py; LSA_GEMM_SKP=0 turns it off)
+        from .engine_skp import SkpStageEngine
+        return SkpStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)
     return StageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)

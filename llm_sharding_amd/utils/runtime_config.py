@@ -41,6 +41,9 @@ KNOBS = {
     "LSA_GEMV_MAX_ROWS": ("env", "diagnostic", "128 (64 for MID_GEMM_SHAPES)",
                           "rows up to which decode projections stay on the GEMVs (profiles/r5_gemv_max_rows_ab.md)"),
     "LSA_GEMM_WR": ("env", "diagnostic", "1", "0 = no gemm_wr routes (profiles/r4_gemm_wr_engine_ab.txt)"),
+    "LSA_GEMM_SKP": ("env", "diagnostic", "1", "0 = no gemm_skp routes: the residual projections keep gemm_sk "
+                     "(profiles/skp_fixup.md)"),
+    "LSA_GEMM_SKP_TUNING": ("env", "diagnostic", "", "path of another gemm_skp tuning table (ops/skp_tuning.txt)"),
     "LSA_ATTN_MIN_CHUNK": ("env", "diagnostic", "256", "shortest split-KV chunk in keys"),
     "LSA_ATTN_MFMA": ("env", "diagnostic", "1", "0 = no MFMA GQA decode kernel"),
     "LSA_ATTN_MFMA_MIN_ITEMS": ("env", "diagnostic", "512", "rows x kv-heads from which GQA decode uses MFMA"),

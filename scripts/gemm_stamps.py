@@ -35,7 +35,7 @@ def main():
     L = ctypes.CDLL(SO)
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.lsa_gemm_sk.argtypes = [vp, i, vp, i, i, i, i, ctypes.POINTER(hip.EpiArgs), i, i, i, i, i, i, i, vp, vp,
-                              ctypes.c_longlong, i, i, vp]
+                              ctypes.c_longlong, i, vp]
     nbuf = max(2, (600 << 20) // (N * K * 2) + 1)
     wps = [packing.pack_b(torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16)) for _ in range(nbuf)]
     x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
