@@ -61,6 +61,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per cached vector (GPU)")
+    ap.add_argument("--kv-layout", default="static", choices=("static", "paged"),
+                    help="KV cache layout: paged = a pool of 64-token pages behind a block table (GPU); the request "
+                         "reserves prompt + --max-new-tokens at admission")
+    ap.add_argument("--kv-pages", type=int, default=0,
+                    help="with --kv-layout paged: pages in the pool (0: one sequence of max_seq tokens, plus the null page)")
     ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
                     help="projection weights on the GPU: bf16, fp8 (OCP e4m3, per-row scales, fp8 lm_head) or int4 "
                          "(symmetric group-128, bf16 lm_head); ignored on the CPU")
@@ -223,11 +228,22 @@ def main(argv=None):
         cfg = get_preset(a.random or "tiny")
         src, tok = RandomSource(cfg), SyntheticByteTokenizer(cfg.vocab_size)
     dt = torch.bfloat16 if a.device.startswith("cuda") else torch.float32
+    max_seq = min(cfg.max_position_embeddings, 4096)
+    kv_pages = None
+    if a.kv_layout == "paged":
+        if spec is not None:
+            raise SystemExit("[ERROR] --speculative does not combine with --kv-layout paged yet (the speculative "
+                             "graph's admission does not reserve pages)")
+        kv_pages = a.kv_pages or max_seq // 64 + 1
+    elif a.kv_pages:
+        raise SystemExit("[ERROR] --kv-pages needs --kv-layout paged")
     t0 = time.perf_counter()
     eng = make_stage_engine(cfg, 0, cfg.num_hidden_layers, a.device, dt, has_embed=True, has_head=True, source=src,
-                            max_seq=min(cfg.max_position_embeddings, 4096), weight_dtype=a.weight_dtype,
-                            kv_dtype=a.kv_dtype)
+                            max_seq=max_seq, weight_dtype=a.weight_dtype, kv_dtype=a.kv_dtype, kv_layout=a.kv_layout,
+                            kv_pages=kv_pages)
     ids = tok(a.prompt, return_tensors="pt")["input_ids"][0]
+    if getattr(eng, "paged", False):  # admission: the whole request's pages, before any graph replays
+        eng.kv_reserve(0, min(eng.max_seq, ids.numel() + a.max_new_tokens))
     if a.choice:
         sp = sampling_from_args(a, [tok.encode(c, add_special_tokens=False) for c in a.choice])
     print(f"[INFO] loaded in {time.perf_counter() - t0:.1f}s; prompt tokens {ids.numel()}")

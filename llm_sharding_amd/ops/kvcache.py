@@ -170,6 +170,8 @@ def fork_jobs(eng, jobs) -> None:
     elsewhere) and set the destinations' host-side lengths."""
     if getattr(eng, "kv8", False):
         raise NotImplementedError("KV fork on an fp8 KV cache: the fork kernel copies bf16 tensors")
+    if getattr(eng, "paged", False):
+        raise NotImplementedError("KV fork on a paged KV cache: the fork kernel copies static tensors")
     if not eng.k_cache:
         return
     n_slots, _, t_max, _ = eng.k_cache[0].shape

@@ -235,8 +235,12 @@ class PipelineStage:
                  microbatches: int, max_seq: int, source, use_graph: bool = True,
                  max_prefill_rows: int = 2048, dtype=torch.bfloat16, p2p=None,
                  split_head: Optional[bool] = None, weight_dtype: str = "bf16", streams: int = 1,
-                 pp_streams: Optional[bool] = None, engine: Optional[StageEngine] = None, kv_dtype: str = "bf16"):
+                 pp_streams: Optional[bool] = None, engine: Optional[StageEngine] = None, kv_dtype: str = "bf16",
+                 kv_layout: str = "static", kv_pages: Optional[int] = None):
         """``kv_dtype="fp8"``: an fp8 KV cache on a GPU stage (runtime/engine_kv8.py).
+        ``kv_layout="paged"``: a pool of ``kv_pages`` 64-token pages behind a block table on a GPU
+        stage (runtime/engine_paged.py); whoever drives the stage reserves a slot's pages
+        (``self.eng.kv_reserve``) before a decode graph writes them.
         ``engine``: reuse a loaded StageEngine (its weights, KV cache and scratch) instead of
         building one - e.g. a batch-1 latency pass after a throughput pass; it must cover this
         stage's layers and hold >= batch x microbatches KV slots."""
@@ -272,7 +276,8 @@ class PipelineStage:
                                          has_head=self.last or (self.split and self.first), source=source,
                                          max_slots=batch * microbatches, max_seq=max_seq,
                                          max_prefill_rows=max(max_prefill_rows, batch), head_cols=head_cols,
-                                         weight_dtype=weight_dtype, kv_dtype=kv_dtype)
+                                         weight_dtype=weight_dtype, kv_dtype=kv_dtype, kv_layout=kv_layout,
+                                         kv_pages=kv_pages)
         H = cfg.hidden_size
         self.h_out = [torch.zeros((batch, H), dtype=self.dtype, device=self.device) for _ in range(microbatches)]
         self.tok_out = [torch.zeros(batch, dtype=torch.int32, device=self.device) for _ in range(microbatches)]
@@ -653,6 +658,9 @@ def _latency_pass(cfg, stage: "PipelineStage", srank: int, pp: int, st, dev, max
     seconds)."""
     eng = stage.eng
     eng.reset(list(range(rows)))
+    if getattr(eng, "paged", False):  # the decode graphs below write these positions
+        for r in range(rows):
+            eng.kv_reserve(r, min(eng.max_seq, prompt_len + LAT_WARMUP + steps + 1))
     b1 = PipelineStage(cfg, srank, pp, st.start, st.end, dev, rows, 1, max_seq, None,
                        use_graph=stage.use_graph, dtype=stage.dtype, p2p=p2p, engine=eng)
     b1.tl = stage.tl
@@ -768,7 +776,8 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
                          verbose: bool = True, weight_dtype: str = "bf16", streams: int = 1,
                          device: str = "cuda", dp: int = 1, latency_steps: int = 0,
                          stage_layers: int = 0, transport: str = "rccl", mid_batch: int = 0,
-                         collect_outputs: bool = False, kv_dtype: str = "bf16") -> Optional[dict]:
+                         collect_outputs: bool = False, kv_dtype: str = "bf16", kv_layout: str = "static",
+                         kv_pages: Optional[int] = None) -> Optional[dict]:
     """``microbatches`` 0 = ``streams`` x stages (every GPU holds ``streams`` micro-batches of
     ``batch`` sequences: weak scaling); ``max_seq`` 0 = what the run needs, rounded up to 64.
 
@@ -793,6 +802,10 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     communicator); the process group is then gloo (barriers and the final statistics only), so
     N ranks may also share ONE GPU (``LOCAL_RANK % device_count``) - a multi-process rehearsal
     of the exact N-stage pipeline on a 1-GPU box. A timed-out hand-off raises (exit non-zero).
+
+    ``kv_layout="paged"``: every stage keeps its KV cache as ``kv_pages`` 64-token pages (default:
+    what the run's sequences fill, plus the null page) and reserves each sequence's whole run
+    before the prefill, so the captured decode steps never meet a null table entry.
 
     ``collect_outputs``: rank 0's result carries ``outputs``, host copies of what the LAST timed
     step left on its stage, taken before any later pass reuses the engine (``last_step_outputs``)."""
@@ -845,8 +858,11 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     need = prompt_len + max(warmup + steps, (LAT_WARMUP + latency_steps) if latency_steps else 0) + 1
     max_seq = max_seq or -(-need // 64) * 64
     S_sets = max(1, min(streams, M))
+    if kv_layout == "paged" and kv_pages is None:
+        kv_pages = batch * M * (-(-need // 64)) + 1
     plan = plan_stages(cfg, pp, kv_tokens=max_seq * batch * M, head_split=pp > 1,
-                       scratch=scratch_bytes(cfg, batch * prompt_len, S_sets, max_seq), kv_dtype=kv_dtype)
+                       scratch=scratch_bytes(cfg, batch * prompt_len, S_sets, max_seq), kv_dtype=kv_dtype,
+                       kv_layout=kv_layout, kv_pages=kv_pages)
     st = plan.stages[srank]
     # this stage's device bytes as the engine will allocate them (profiles/memory_table.md)
     V = cfg.head_rows
@@ -854,7 +870,7 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     head_rows = (v1 if st.has_head else 0) + (V - v1 if (pp > 1 and st.has_embed) else 0)
     mem_pred = stage_memory(cfg, st.n_layers, slots=batch * M, max_seq=max_seq, prefill_rows=batch * prompt_len,
                             has_embed=st.has_embed, head_rows=head_rows, scratch_sets=S_sets, io_rows=batch * M,
-                            weight_dtype=weight_dtype, kv_dtype=kv_dtype)
+                            weight_dtype=weight_dtype, kv_dtype=kv_dtype, kv_layout=kv_layout, kv_pages=kv_pages)
     if need > max_seq:
         raise ValueError(f"prompt+warmup+steps ({need}) exceeds max_seq {max_seq}")
     if verbose and rank == 0:
@@ -891,7 +907,11 @@ def run_decode_benchmark(model: str = "llama2-7b", n_gpus: int = 1, steps: int =
     stage = PipelineStage(cfg, srank, pp, st.start, st.end, dev, batch, M, max_seq,
                           RandomSource(cfg, seed), use_graph=use_graph,
                           max_prefill_rows=batch * prompt_len, weight_dtype=weight_dtype, streams=streams,
-                          dtype=torch.bfloat16 if gpu else torch.float32, p2p=p2p, kv_dtype=kv_dtype)
+                          dtype=torch.bfloat16 if gpu else torch.float32, p2p=p2p, kv_dtype=kv_dtype,
+                          kv_layout=kv_layout, kv_pages=kv_pages)
+    if getattr(stage.eng, "paged", False):
+        for slot in range(batch * M):
+            stage.eng.kv_reserve(slot, prompt_len + warmup + steps + 1)
     if dp > 1:  # trace files are named by rank: use the global one
         stage.tl = tracing.from_env(rank, dev if gpu else "cpu")
     sync()

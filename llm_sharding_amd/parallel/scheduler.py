@@ -78,7 +78,8 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
                 layer_costs: Optional[Sequence[float]] = None, embed_cost: Optional[float] = None,
                 head_cost: Optional[float] = None, kv_tokens: int = 0, elem_bytes: int = 2,
                 min_layers: int = 1, head_split: bool = False, scratch: float = 0.0,
-                stage_overhead: float = 0.0, kv_dtype: str = "bf16") -> Plan:
+                stage_overhead: float = 0.0, kv_dtype: str = "bf16", kv_layout: str = "static",
+                kv_pages: Optional[int] = None) -> Plan:
     """Exact min-max contiguous partition. ``devices`` is a list (chain order) or a count.
     ``head_split``: the lm_head is shared by the last and the first stage (pipeline.py), so each
     carries half of its cost and memory. ``scratch``: per-stage engine scratch bytes
@@ -86,7 +87,11 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
     ``stage_overhead``: fixed cost of one stage step (measured costs:
     node_profiler.costs_for_planner), added to every stage before its device's speed factor.
     ``kv_dtype="fp8"``: a cached token costs :func:`kv_token_bytes` per layer, and every stage also
-    holds one bf16 staging layer over its ``kv_tokens`` (runtime/engine_kv8.py), counted with its scratch."""
+    holds one bf16 staging layer over its ``kv_tokens`` (runtime/engine_kv8.py), counted with its scratch.
+    ``kv_layout="paged"``: a layer holds ``kv_pages`` pages of 64 tokens instead of ``kv_tokens``
+    tokens; the staging layer over ``kv_tokens`` (slots x max_seq) and the block table count with
+    the scratch (runtime/engine_paged.py)."""
+    _check_layout(kv_layout, kv_pages, kv_dtype)
     if isinstance(devices, int):
         devices = [DeviceSpec() for _ in range(devices)]
     n, L = len(devices), cfg.num_hidden_layers
@@ -100,6 +105,9 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
     kv_per_layer = float(kv_token_bytes(cfg, elem_bytes, kv_dtype)) * kv_tokens
     if kv_dtype == "fp8":
         scratch = scratch + float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * kv_tokens
+    if kv_layout == "paged":
+        kv_per_layer = float(kv_token_bytes(cfg, elem_bytes)) * kv_pages * KV_PAGE
+        scratch = scratch + float(cfg.kv_bytes_per_token_per_layer(elem_bytes)) * kv_tokens + 4.0 * (kv_tokens // KV_PAGE)
     emb_bytes = float(cfg.vocab_size * cfg.hidden_size * elem_bytes)
     head_bytes = emb_bytes if not cfg.tie_word_embeddings else 0.0
 
@@ -161,6 +169,39 @@ def plan_stages(cfg: LlamaConfig, devices: Sequence[DeviceSpec] | int, *,
     return plan
 
 
+KV_PAGE = 64  # tokens per page of the paged KV cache (ops/kv_paged.py PAGE)
+
+
+def _check_layout(kv_layout: str, kv_pages, kv_dtype: str = "bf16") -> None:
+    if kv_layout not in ("static", "paged"):
+        raise ValueError(f"kv_layout must be static or paged, got {kv_layout!r}")
+    if kv_layout == "paged":
+        if kv_dtype != "bf16":
+            raise ValueError(f"kv_layout='paged' holds bf16 pages, got kv_dtype={kv_dtype!r}")
+        if kv_pages is None or int(kv_pages) < 2:
+            raise ValueError(f"kv_layout='paged' needs kv_pages >= 2, got {kv_pages}")
+    elif kv_pages is not None:
+        raise ValueError("kv_pages needs kv_layout='paged'")
+
+
+def kv_pages_for_memory(cfg: LlamaConfig, n_layers: int, slots: int, max_seq: int, mem_bytes: float,
+                        weight_bytes: float, reserve_bytes: float = 8e9, elem_bytes: int = 2) -> int:
+    """Pages of the paged KV cache that fit a stage of ``n_layers`` layers next to its weights: the
+    counterpart of :func:`kv_slots_for_memory`. The one bf16 staging layer over all ``slots`` and
+    the block table are charged first; every page then costs 64 tokens on each layer. No more
+    pages than ``slots`` full sequences could fill (plus the null page) are returned."""
+    if max_seq < KV_PAGE or max_seq % KV_PAGE:
+        raise ValueError(f"kv_layout='paged' needs max_seq to be a multiple of {KV_PAGE}, got {max_seq}")
+    tok = float(cfg.kv_bytes_per_token_per_layer(elem_bytes))
+    fixed = tok * slots * max_seq + 4.0 * slots * (max_seq // KV_PAGE)
+    free = mem_bytes - reserve_bytes - weight_bytes - fixed
+    pages = int(free // (tok * n_layers * KV_PAGE)) if free > 0 else 0
+    if pages < 2:
+        raise ValueError(f"no room for a paged KV cache of {slots} slots x {max_seq} tokens x {n_layers} layers "
+                         f"({free / 1e9:.1f} GB free after weights, staging layer and table)")
+    return min(pages, slots * (max_seq // KV_PAGE) + 1)
+
+
 def kv_token_bytes(cfg: LlamaConfig, elem_bytes: int = 2, kv_dtype: str = "bf16") -> int:
     """Bytes one cached token costs per layer: ``2 * n_kv * hd * elem_bytes``, or with
     ``kv_dtype="fp8"`` ``n_kv * (2 * hd + 8)`` (8448 against 16384 for Llama-2-7B)."""
@@ -190,6 +231,28 @@ def size_kv_slots(cfg: LlamaConfig, world: int, max_seq: int, mem_bytes: float, 
             break
         plan = nxt
     return batch, plan_stages(cfg, world, kv_tokens=max_seq * (batch * M + prefix_slots), kv_dtype=kv_dtype)
+
+
+def size_kv_pages(cfg: LlamaConfig, world: int, slots: int, max_seq: int, mem_bytes: float,
+                  reserve_bytes: float) -> tuple:
+    """(pages per stage, plan): the paged KV cache of a ``world``-stage server with ``slots`` slots sized
+    from the devices' HBM, the counterpart of :func:`size_kv_slots`. The page budget moves the layer
+    boundaries, so pages and plan are iterated until the plan the pages were sized for is the plan they
+    give (the returned pair always match each other). The planner checks the stages against the same
+    ``mem_bytes - reserve_bytes`` the pages were sized for, not against ``DeviceSpec``'s defaults."""
+    devices = [DeviceSpec(mem_bytes=mem_bytes, reserve_bytes=reserve_bytes) for _ in range(world)]
+    plan = plan_stages(cfg, devices)
+    for _ in range(8):
+        pages = min(kv_pages_for_memory(cfg, s.n_layers, slots, max_seq, mem_bytes, s.weight_bytes, reserve_bytes)
+                    for s in plan.stages)
+        nxt = plan_stages(cfg, devices, kv_tokens=max_seq * slots, kv_layout="paged", kv_pages=pages)
+        if nxt.ranges() == plan.ranges():
+            return pages, nxt
+        plan = nxt
+    # no fixed point in 8 rounds: size the pages for the last plan's stages and keep that plan
+    pages = min(kv_pages_for_memory(cfg, s.n_layers, slots, max_seq, mem_bytes, s.weight_bytes, reserve_bytes)
+                for s in plan.stages)
+    return pages, plan
 
 
 def kv_slots_for_memory(cfg: LlamaConfig, n_layers: int, max_seq: int, mem_bytes: float,
@@ -240,7 +303,8 @@ def scratch_bytes(cfg: LlamaConfig, rows: int, sets: int = 1, max_seq: int = 409
 
 def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, prefill_rows: int,
                  has_embed: bool = False, head_rows: int = 0, scratch_sets: int = 1,
-                 io_rows: int = 0, elem_bytes: int = 2, weight_dtype: str = "bf16", kv_dtype: str = "bf16") -> dict:
+                 io_rows: int = 0, elem_bytes: int = 2, weight_dtype: str = "bf16", kv_dtype: str = "bf16",
+                 kv_layout: str = "static", kv_pages: Optional[int] = None) -> dict:
     """Device bytes of one pipeline stage as the engine allocates them (weights, static KV cache,
     scratch) - the memory table the bench's stage sizing relies on (profiles/memory_table.md).
     ``head_rows``: lm_head rows held on this stage (split head: a part of the vocabulary);
@@ -250,7 +314,10 @@ def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, p
     projection-sized bf16 dequantisation buffer per scratch set. Any other value ("fp8" too, which
     this table never modelled) counts the weights at ``elem_bytes``. ``kv_dtype="fp8"``: ``kv`` counts
     ``n_kv * (2 * hd + 8)`` bytes per token and layer, and ``scratch`` grows by the one bf16 staging
-    layer (runtime/engine_kv8.py)."""
+    layer (runtime/engine_kv8.py). ``kv_layout="paged"``: ``kv`` counts ``kv_pages`` pages of 64
+    tokens per layer, whatever ``slots`` and ``max_seq`` are, and ``scratch`` grows by the bf16 staging
+    layer over ``slots * max_seq`` and the int32 block table (runtime/engine_paged.py)."""
+    _check_layout(kv_layout, kv_pages, kv_dtype)
     H = cfg.hidden_size
     w = n_layers * cfg.layer_bytes(elem_bytes)
     w_scratch = 0
@@ -267,6 +334,9 @@ def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, p
     scratch = scratch_bytes(cfg, prefill_rows, scratch_sets, max_seq, head_rows) + w_scratch
     if kv_dtype == "fp8":
         scratch += cfg.kv_bytes_per_token_per_layer(elem_bytes) * slots * max_seq
+    if kv_layout == "paged":
+        kv = n_layers * kv_token_bytes(cfg, elem_bytes) * kv_pages * KV_PAGE
+        scratch += cfg.kv_bytes_per_token_per_layer(elem_bytes) * slots * max_seq + 4 * slots * (max_seq // KV_PAGE)
     io = io_rows * (H * elem_bytes + 4 + 8)
     return {"weights": float(w), "kv": float(kv), "scratch": float(scratch), "io": float(io),
             "total": float(w + kv + scratch + io)}

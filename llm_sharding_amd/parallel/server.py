@@ -163,7 +163,14 @@ class PipelineServer:
                  prefill_budget: int = 2048, use_graph: bool = True, dtype=torch.bfloat16,
                  ctrl_group=None, p2p=None, causal: bool = True, verbose: bool = False, streams: int = 1,
                  prefix_slots: int = 0, prefix_min_match: int = PREFIX_MIN_MATCH, state_rows: int = 256,
-                 vocab_bytes=None, dfa_rows: int = 4096, kv_dtype: str = "bf16", json_max_ws: int = 2):
+                 vocab_bytes=None, dfa_rows: int = 4096, kv_dtype: str = "bf16", json_max_ws: int = 2,
+                 kv_layout: str = "static", kv_pages: Optional[int] = None):
+        """``kv_layout="paged"``: the KV cache of a GPU stage is a pool of ``kv_pages`` 64-token pages
+        (runtime/engine_paged.py; default: what every slot at ``max_seq`` would fill). Every rank
+        drives its own ``PagePool`` from the command stream (:meth:`_exec_body`); rank 0 admits a
+        request only while the pages of all admitted requests, each ``pages_for(prompt +
+        max_new_tokens)``, fit the pool. On a CPU stage the cache stays static and the same
+        accounting runs."""
         self.cfg, self.rank, self.world = cfg, rank, world
         if isinstance(json_max_ws, bool) or not isinstance(json_max_ws, int) or not 0 <= json_max_ws <= 8:
             raise ValueError(f"json_max_ws must be an integer in [0, 8], got {json_max_ws!r}")
@@ -173,6 +180,21 @@ class PipelineServer:
         if kv_dtype == "fp8" and int(prefix_slots) > 0:
             raise ValueError("prefix_slots > 0 needs kv_dtype='bf16': the KV fork kernel copies bf16 tensors")
         self.kv_dtype = kv_dtype
+        from ..ops import kv_paged
+        from ..runtime.engine_paged import check_kv_layout
+        check_kv_layout(kv_layout, kv_pages, "bf16", kv_dtype)
+        self.kv_paged = kv_layout == "paged"
+        if self.kv_paged:
+            kv_paged.check_max_seq(int(min(max_seq, cfg.max_position_embeddings)))
+            if int(prefix_slots) > 0:
+                raise ValueError("prefix_slots > 0 needs kv_layout='static': the KV fork kernel copies static tensors")
+            if kv_pages is None:
+                kv_pages = batch * microbatches * (int(min(max_seq, cfg.max_position_embeddings)) // kv_paged.PAGE) + 1
+        self.kv_pages = None if kv_pages is None else int(kv_pages)
+        self.kv_pool = None            # this rank's page allocator (the paged engine's own on a GPU)
+        self.kv_len: Dict[int, int] = {}   # this rank's count of every live slot's length
+        self.kv_held: Dict[int, int] = {}  # rank 0: pages reserved by the request in each slot, admission to finish
+        self.peak_in_flight = 0
         # prefix pool: engine slots >= B * M, never decoded, in no micro-batch and no graph
         self.P = int(prefix_slots)
         if self.P < 0 or int(prefix_min_match) < 1:
@@ -248,10 +270,53 @@ class PipelineServer:
     # ------------------------------------------------------------------ engine (re)build
     def _build_engine(self, start: int, end: int) -> StageEngine:
         from ..runtime.engine_int4 import make_stage_engine
-        return make_stage_engine(self.cfg, start, end, self.device, self.dtype, has_embed=self.first,
+        eng = make_stage_engine(self.cfg, start, end, self.device, self.dtype, has_embed=self.first,
                                  has_head=self.last, source=self.source, max_slots=self.B * self.M + self.P,
                                  max_seq=self.max_seq, max_prefill_rows=max(self.budget, self.B), causal=self.causal,
-                                 kv_dtype=self.kv_dtype)
+                                 kv_dtype=self.kv_dtype, kv_layout="paged" if self.kv_paged else "static",
+                                 kv_pages=self.kv_pages)
+        if self.kv_paged:  # a fresh engine: every page is free again
+            from ..ops import kv_paged
+            self.kv_pool = eng.pool if getattr(eng, "paged", False) else kv_paged.PagePool(self.kv_pages, eng.max_slots,
+                                                                                          eng.max_seq)
+            self.kv_len = {}
+            self.kv_held = {}
+        return eng
+
+    # ------------------------------------------------------------------ pages (every rank)
+    def _kv_reserve(self, slot: int, n_tokens: int) -> None:
+        if getattr(self.eng, "paged", False):
+            self.eng.kv_reserve(slot, n_tokens)  # (pushes the changed table entries)
+        else:
+            self.kv_pool.reserve(slot, n_tokens)
+
+    def _kv_release(self, slot: int) -> None:
+        self.kv_len.pop(slot, None)
+        if getattr(self.eng, "paged", False):
+            self.eng.kv_release(slot)
+        else:
+            self.kv_pool.release(slot)
+
+    def _apply_resets(self, resets) -> None:
+        for s in resets:
+            self._set_pos(s, 0)
+            if self.kv_paged and s < self.B * self.M:
+                self._kv_release(s)
+
+    def _kv_account(self, cmd, mb, items) -> None:
+        """The pages this command writes, reserved before it runs (its resets have released theirs:
+        a finished request's slot is reset by the first command after it, whoever takes the slot).
+        PREFILL item (slot, p0, n, emit): ``p0 + n`` tokens. DECODE: one more token for every live
+        slot of the micro-batch."""
+        if cmd == CMD_PREFILL:
+            for (s, p0, n, _) in items:
+                self.kv_len[s] = p0 + n
+                self._kv_reserve(s, p0 + n)
+        elif cmd == CMD_DECODE:
+            for s in self._slots(mb):
+                if s in self.kv_len:
+                    self.kv_len[s] = min(self.kv_len[s] + 1, self.eng.max_seq)
+                    self._kv_reserve(s, self.kv_len[s])
 
     def _build_graphs(self) -> None:
         for k in range(1, self.S):
@@ -542,8 +607,9 @@ class PipelineServer:
 
     def _exec_body(self, cmd, mb, items, resets, ids=None):
         eng, H = self.eng, self.cfg.hidden_size
-        for s in resets:
-            self._set_pos(s, 0)
+        self._apply_resets(resets)
+        if self.kv_paged:
+            self._kv_account(cmd, mb, items)
         if cmd == CMD_FORK:  # items (src, dst, len, 0) on this stage's layers; nothing returns
             from ..ops.kvcache import MAX_FANOUT, fork_jobs
             by_src: Dict[tuple, list] = {}
@@ -671,6 +737,9 @@ class PipelineServer:
         if len(ids) + max_new_tokens > self.eng.max_seq:
             raise ValueError(f"prompt ({len(ids)}) + max_new_tokens ({max_new_tokens}) exceeds max_seq "
                              f"{self.eng.max_seq}")
+        if self.kv_paged and self.kv_pool.pages_for(len(ids) + max_new_tokens) > self.kv_pages - 1:
+            raise ValueError(f"prompt ({len(ids)}) + max_new_tokens ({max_new_tokens}) needs "
+                             f"{self.kv_pool.pages_for(len(ids) + max_new_tokens)} pages, the pool has {self.kv_pages - 1}")
         constraint = None
         if sampling is not None and sampling.constrained:
             from ..runtime.sampling import _check_full_head, compile_constraints
@@ -888,6 +957,7 @@ class PipelineServer:
                 if warn:
                     print(f"[WARN] request {r.rid}: {warn}", flush=True)
             mb = r.slot // self.B
+            self.kv_held.pop(r.slot, None)
             del self.by_slot[r.slot]
             self.cur_tok.pop(r.slot, None)
             self.pending_resets[mb].append(r.slot)
@@ -958,6 +1028,11 @@ class PipelineServer:
         for s in self._free_slots(mb):
             if not self.waiting or self._replan is not None:
                 break
+            if self.kv_paged:  # admission by reservation: the head of the queue waits for its pages, in place
+                need = self.kv_pool.pages_for(len(self.waiting[0].input_ids) + self.waiting[0].max_new_tokens)
+                if sum(self.kv_held.values()) + need > self.kv_pages - 1:
+                    break
+                self.kv_held[s] = need
             r = self.waiting.pop(0)
             if r.sampling is not None:
                 want = {c.name: c.wants(r.sampling) for c in STAGE_CLASSES}
@@ -969,7 +1044,10 @@ class PipelineServer:
                     self._enable_logprobs()
             r.slot, r.state, r.prefilled = s, PREFILLING, 0
             self.by_slot[s] = r
-            if s in resets:
+            if s in resets and not self.kv_paged:
+                # (paged: the reset always travels with this call's command, the new request's first
+                # prefill item may not - the budget - and the old request's pages are released by the
+                # reset alone: its reservation was dropped on rank 0 when it finished)
                 resets.remove(s)
             if self.P:
                 self._attach(r)
@@ -979,6 +1057,7 @@ class PipelineServer:
             # requests of mb whose pool entry is still to be filled: the fill rides with mb's prefills
             fills = [r.entry for r in (self.by_slot.get(s) for s in self._slots(mb))
                      if r is not None and r.state == FORKING and r.entry.filler is r and not r.entry.ready]
+        self.peak_in_flight = max(self.peak_in_flight, len(self.by_slot))
         pre = [self.by_slot[s] for s in self._slots(mb) if s in self.by_slot and self.by_slot[s].state == PREFILLING]
         if pre or fills:
             items, ids, info, budget = [], [], [], self.budget
@@ -1040,8 +1119,7 @@ class PipelineServer:
         self._bcast_header(hdr)
         if not run:
             with self._mb_ctx(mb):
-                for s in resets:
-                    self._set_pos(s, 0)
+                self._apply_resets(resets)
             return
         local = self._exec(cmd, mb, items, resets, ids=ids)
         self.outstanding[mb] = (cmd, info, local)
@@ -1098,8 +1176,7 @@ class PipelineServer:
             if cmd == CMD_STOP:
                 break
             if cmd == 0:
-                for s in resets:
-                    self._set_pos(s, 0)
+                self._apply_resets(resets)
                 continue
             self._exec(cmd, mb, items, resets)
         self._flush_sends()
@@ -1126,6 +1203,7 @@ class PipelineServer:
             "ttft_ms_p50": _percentile([r.ttft_ms for r in done], 0.5),
             "tpot_ms_p50": _percentile([r.tpot_ms for r in done if len(r.output_ids) > 1], 0.5),
             "tpot_ms_p90": _percentile([r.tpot_ms for r in done if len(r.output_ids) > 1], 0.9),
+            "peak_in_flight": self.peak_in_flight,  # most requests holding a slot at once
             # prefix pool: requests that forked K/V computed for another request and the prefill tokens
             # that saved them, pool entries filled / evicted, declared prefixes that found every slot pinned
             **self.prefix_stats,

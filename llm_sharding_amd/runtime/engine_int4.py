@@ -255,14 +255,23 @@ class Int4StageEngine(StageEngine):
 
 
 def make_stage_engine(cfg, start: int, end: int, device="cpu", dtype=torch.bfloat16, *, weight_dtype: str = "bf16",
-                      kv_dtype: str = "bf16", **kw) -> StageEngine:
+                      kv_dtype: str = "bf16", kv_layout: str = "static", kv_pages=None, **kw) -> StageEngine:
     """``StageEngine`` for ``weight_dtype`` "bf16" / "fp8" (anything else raises there),
     ``Int4StageEngine`` for "int4"; ``kv_dtype="fp8"`` on a GPU: ``Fp8KVStageEngine``
-    (runtime/engine_kv8.py; bf16 or fp8 weights); the default dtypes on a GPU: ``SkpStageEngine``
-    (runtime/engine_skp.py, StageEngine plus the gemm_skp route). A CPU engine ignores ``kv_dtype`` as it ignores
-    ``weight_dtype``; a value other than "bf16" / "fp8" raises on every device."""
+    (runtime/engine_kv8.py; bf16 or fp8 weights); ``kv_layout="paged"`` on a GPU:
+    ``PagedKVStageEngine`` with a pool of ``kv_pages`` pages (runtime/engine_paged.py; bf16 or fp8
+    weights, bf16 KV); the default dtypes and layout on a GPU: ``SkpStageEngine``
+    (runtime/engine_skp.py, StageEngine plus the gemm_skp route). A CPU engine ignores ``kv_dtype``
+    and ``kv_layout`` as it ignores ``weight_dtype``; a bad value or combination raises on every device."""
     from .engine_kv8 import Fp8KVStageEngine, check_kv_dtype
+    from .engine_paged import PagedKVStageEngine, check_kv_layout
     check_kv_dtype(kv_dtype, weight_dtype)
+    check_kv_layout(kv_layout, kv_pages, weight_dtype, kv_dtype)
+    if kv_layout == "paged":
+        from ..ops import kv_paged
+        kv_paged.check_max_seq(int(min(kw.get("max_seq", 2048), cfg.max_position_embeddings)))
+        if torch.device(device).type == "cuda":
+            return PagedKVStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, kv_pages=kv_pages, **kw)
     if kv_dtype == "fp8" and torch.device(device).type == "cuda":
         return Fp8KVStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)
     if weight_dtype == "int4":

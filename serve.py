@@ -109,6 +109,11 @@ def main():
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per cached vector "
                          "(8448 instead of 16384 bytes per Llama-2-7B token and layer; no --prefix-slots)")
+    ap.add_argument("--kv-layout", default="static", choices=("static", "paged"),
+                    help="KV cache layout: paged = a pool of 64-token pages behind a block table; a request holds the "
+                         "pages of prompt + max_new_tokens instead of a max_seq slot (bf16 KV; no --prefix-slots, no --n)")
+    ap.add_argument("--kv-pages", type=int, default=0, metavar="N",
+                    help="with --kv-layout paged: pages in every stage's pool (0: sized from the free HBM)")
     argv = sys.argv[1:]
     for i in range(len(argv) - 1):  # a pattern that starts with '-' is no option
         if argv[i] == "--regex":
@@ -140,6 +145,12 @@ def main():
         ctrl = dist.new_group(backend="gloo")
     cfg, source = rc.model_and_source()
     M = rc.microbatches or max(2, world)
+    paged = a.kv_layout == "paged"
+    if a.kv_pages and not paged:
+        raise SystemExit("[ERROR] --kv-pages needs --kv-layout paged")
+    if paged and rc.batch == 0:
+        raise SystemExit("[ERROR] --kv-layout paged sizes its pages from the HBM (--kv-pages 0), not its slots: "
+                         "give --batch")
     if rc.batch == 0:  # size the KV cache from this GPU's HBM
         from llm_sharding_amd.parallel.scheduler import scratch_bytes, size_kv_slots
         mem = torch.cuda.get_device_properties(dev).total_memory if gpu else 64e9
@@ -148,7 +159,20 @@ def main():
         # (the KV budget moves layer boundaries: iterated to a fixed point, priced by the cache format)
         rc.batch, _ = size_kv_slots(cfg, world, rc.max_seq, mem, reserve, M, a.prefix_slots, a.kv_dtype)
         log.info(f"KV cache sized from {mem / 1e9:.0f} GB HBM: {rc.batch} slots x {M} micro-batches")
-    plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots), kv_dtype=a.kv_dtype)
+    if paged:
+        from llm_sharding_amd.parallel.scheduler import scratch_bytes, size_kv_pages
+        kv_pages = a.kv_pages
+        if kv_pages:
+            plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * rc.batch * M, kv_layout="paged", kv_pages=kv_pages)
+        else:  # what fits every stage next to its weights, its staging layer and its scratch (a fixed point:
+            # the page budget moves the layer boundaries)
+            mem = torch.cuda.get_device_properties(dev).total_memory if gpu else 64e9
+            reserve = 8e9 + scratch_bytes(cfg, rc.prefill_budget, sets=max(1, rc.streams))
+            kv_pages, plan = size_kv_pages(cfg, world, rc.batch * M, rc.max_seq, mem, reserve)
+            log.info(f"paged KV cache sized from {mem / 1e9:.0f} GB HBM: {kv_pages} pages of 64 tokens per stage")
+    else:
+        kv_pages = None
+        plan = plan_stages(cfg, world, kv_tokens=rc.max_seq * (rc.batch * M + a.prefix_slots), kv_dtype=a.kv_dtype)
     st = plan.stages[rank]
     if rank == 0:
         log.info(f"{cfg.name}: {world} stage(s) {plan.ranges()}, {M} x {rc.batch} slots")
@@ -172,7 +196,8 @@ def main():
                          max_seq=rc.max_seq, prefill_budget=rc.prefill_budget, use_graph=rc.use_graph,
                          dtype=rc.torch_dtype(dev) if gpu else torch.float32, ctrl_group=ctrl, causal=rc.causal,
                          streams=rc.streams, prefix_slots=a.prefix_slots, state_rows=a.state_rows,
-                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows, kv_dtype=a.kv_dtype, json_max_ws=a.json_max_ws)
+                         vocab_bytes=vocab_bytes, dfa_rows=a.dfa_rows, kv_dtype=a.kv_dtype, json_max_ws=a.json_max_ws,
+                         kv_layout=a.kv_layout, kv_pages=kv_pages)
     if rank != 0:
         srv.serve()
     elif a.requests:
@@ -201,7 +226,7 @@ def main():
         s.update({"metric": "serving_output_tokens_per_sec", "n_gpus": world, "model": cfg.name,
                   "requests": a.requests * a.n, "prompt_len": a.prompt_len, "max_new_tokens": rc.max_new_tokens,
                   "prefix_slots": a.prefix_slots, "shared_prefix_len": len(shared), "n": a.n,
-                  "slots": rc.batch * M, "microbatches": M})
+                  "slots": rc.batch * M, "microbatches": M, "kv_layout": a.kv_layout, "kv_pages": kv_pages})
         print(json.dumps(s), flush=True)
     else:
         stop_evt = threading.Event()
