@@ -479,6 +479,16 @@ def _sk_partial() -> dict:
     return _SK_PARTIAL
 
 
+def _nearest_tuned(entries, M: int, tile_rows: int):
+    """The (m, value) entry of ``entries`` whose measured row count m covers the same number of
+    ``tile_rows``-row tiles as M and is nearest to M, or None. Of two entries at the same distance
+    the lower m wins (then the first listed): the key holds row counts only, so what the entries
+    carry (a plan, a list, None) is never compared."""
+    mt = -(-M // tile_rows)
+    cands = [e for e in entries if -(-e[0] // tile_rows) == mt]
+    return min(cands, key=lambda e: (abs(e[0] - M), e[0])) if cands else None
+
+
 @functools.lru_cache(maxsize=4096)
 def gemm_sk_plan(M: int, N: int, K: int, tuned: bool = True) -> tuple:
     """(bn, grid, dp, split, bm) for ``gemm_sk``. Grid = one workgroup per CU (the kernel holds
@@ -486,15 +496,15 @@ def gemm_sk_plan(M: int, N: int, K: int, tuned: bool = True) -> tuple:
     equal K splits (concurrent workgroups stream the same K offsets: L2 reuse) or by stream-K.
 
     ``tuned``: a shape measured by scripts/tune_gemm_sk.py (same N, K and the same number of
-    128-row tiles, nearest M) takes its measured winner (bm = 256 unless the entry says 128). Otherwise a cost model: per 64-deep K
+    128-row tiles, nearest M; of two measured row counts at the same distance the lower one: only
+    distances are compared, never the entries) takes its measured winner (bm = 256 unless the entry says 128). Otherwise a cost model: per 64-deep K
     step ~1.5 us for a 256x256 tile, ~1.1 us for 256x128 (scripts/bench_gemm_sk.py); stream-K's
     staggered K offsets lose ~2x of that to L2 misses; every extra partial costs one 256 x bn
     fp32 slab read (~100 GB/s per workgroup)."""
     if tuned:
-        m128 = -(-M // 128)
-        cands = [(abs(m - M), cfg) for m, cfg in _sk_tuned().get((N, K), ()) if -(-m // 128) == m128]
-        if cands:
-            cfg = min(cands)[1]
+        cfg = _nearest_tuned(_sk_tuned().get((N, K), ()), M, 128)
+        if cfg is not None:
+            cfg = cfg[1]
             if N % (16 if cfg[0] == 192 else cfg[0]) == 0:
                 return (cfg[0], N_CU, cfg[2], cfg[3], cfg[4] if len(cfg) > 4 else SK_BM)
     nkt = K // 64
@@ -757,17 +767,15 @@ def resid_rmsnorm_partials(h: torch.Tensor, partials: torch.Tensor, S: int, rows
 def gemm_sk_partial_plan(M: int, N: int, K: int) -> Optional[tuple]:
     """(bn, split) for a residual projection run as EPI_PARTIAL + resid_rmsnorm_partials, or
     None when the fused EPI_RESID plan is better. Tuned shapes carry a measured ``partial``
-    entry (scripts/tune_gemm_sk.py); otherwise None (no partials above PARTIAL_MAX_ROWS)."""
+    entry (scripts/tune_gemm_sk.py): the nearest measured row count with the same number of
+    256-row tiles decides, the lower one of two at the same distance (:func:`_nearest_tuned`);
+    otherwise None (no partials above PARTIAL_MAX_ROWS)."""
     if M > PARTIAL_MAX_ROWS:
         return None
     if _PARTIAL_FORCE is not None:  # force_partial_plan(): tests pin the mode
         return None if _PARTIAL_FORCE is False else _PARTIAL_FORCE
-    mt = -(-M // SK_BM)
-    cands = [(abs(m - M), pp) for m, pp in _sk_partial().get((N, K), ()) if -(-m // SK_BM) == mt]
-    if not cands:
-        return None
-    pp = min(cands)[1]
-    return None if pp is None else tuple(pp)
+    e = _nearest_tuned(_sk_partial().get((N, K), ()), M, SK_BM)
+    return None if e is None or e[1] is None else tuple(e[1])
 
 
 PARTIAL_MAX_ROWS = 1024   # rows of the engine's split-K partial buffer
