@@ -4,6 +4,8 @@
 //   lsa_kvp_append          bf16 staging cells (slot[m], h, pos[m], :) -> the cell's page
 //   lsa_kvp_gather          pages of [0, len) of the named slots -> the bf16 staging layer
 //   lsa_attn_decode_paged   lsa_attn_decode (kernels/attention.hip, attn_body.h) over the pages
+//   lsa_attn_decode_mfma_paged   lsa_attn_decode_mfma (kernels/attn_prefill.hip gqa_decode_kernel)
+//                           over the pages: GQA batches of many (row, kv-head) items
 //
 // Format (ops/kv_paged.py states it in torch). One layer holds kp, vp: bf16 [n_pages, n_kv, 64, hd];
 // the engine holds one table: int32 [n_slots, t_max / 64]. Token t of slot s lives in page
@@ -24,6 +26,12 @@
 // read the chunk's first key instead, as in the static body. Measured against it and left out
 // (profiles/kv_paged.md): a scalar load per load instruction (wave id through readfirstlane, the
 // entry of k0 kept for those lanes), 0.3-1.5 points slower on the batched shapes.
+//
+// Table fetch of the MFMA kernel: a 32-key sub-block needs one entry, the same for all lanes. Each
+// lane holds entry `lane` of a 64-page window of the slot's row (one vector load per wave per 4096
+// keys) and the sub-block's entry is a readlane: no table load in the K/V loop. Measured
+// (profiles/kv_paged.md): -2.1 ... +3.4 % against lsa_attn_decode_mfma at 512 rows. Not built and
+// not measured: prefetching the entry of sub-block sb + 2 NW while sb computes.
 #include "../kernels/common.h"
 
 #include <type_traits>
@@ -399,7 +407,309 @@ int kvp_dispatch(int g, const KvpAttnArgs& a) {
   }
 }
 
+// ------------------------------------------------------------------------------ GQA attention on MFMA
+// attn_prefill.hip's gqa_decode_kernel<HD, NW> with the K/V operand behind the table: one workgroup
+// per (row, kv-head), the G query heads as the 16 MFMA columns, wave w on the 32-key sub-blocks
+// w, w + NW, ..., V by non-temporal LDS-DMA into the wave's private double buffer (swizzled image,
+// read back transposed), K straight into registers, the counted vmcnt(PPW + NKL), the merge of the
+// NW states through LDS. Every floating-point operation is the static kernel's, in its order.
+//
+// A sub-block lies in one page, so stage() needs one table entry, the same for all 64 lanes, and
+// from it one 64-bit page base that the K and V addresses of all lanes share (an SGPR base under the
+// static kernel's per-lane 32-bit offsets). The entry never comes from a load inside the loop: lane
+// i holds entry 64 * win + i of the slot's row (ONE vector load per window of 64 pages = 4096
+// keys = 128 sub-blocks, guarded by the row's t_max / 64 entries) and stage() takes the entry of
+// sub-block sb with v_readlane_b32 at lane (sb / 2) % 64. The reload when sb enters the next window
+// is a wave-uniform branch taken once per 4096 keys; the readlane behind it drains vmcnt once, which
+// the counted wait that follows tolerates (everything older has then retired).
+template <int HD>
+LSA_DEVICE int kvm_swz(int r) {
+  if constexpr (HD == 128) return ((r & 3) << 2) ^ (((r >> 2) & 3) << 1);
+  else return (r >> 1) & 7;
+}
+// byte offset of 16-B chunk ch of row r in a [32][HD] bf16 image
+template <int HD>
+LSA_DEVICE int kvm_sw_off(int r, int ch) {
+  return r * (HD * 2) + ((ch ^ kvm_swz<HD>(r)) << 4);
+}
+LSA_DEVICE void kvm_glds16_nt(const void* src, unsigned char* lds_base) {
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 2);
+}
+typedef short kvm_v4s_t __attribute__((ext_vector_type(4)));
+
+template <int HD, int NW>
+__global__ __launch_bounds__(NW * 64) void gqa_decode_paged_kernel(
+    const bf16_raw* __restrict__ q, int ldq, const bf16_raw* __restrict__ kp, const bf16_raw* __restrict__ vp,
+    const int* __restrict__ table, int n_pages, const int* __restrict__ dslot, const int* __restrict__ dpos,
+    const int* __restrict__ dkvlen, int n_heads, int n_kv, int t_max, float scale_log2, bf16_raw* __restrict__ out,
+    int ldo) {
+  constexpr int SB = 32;                       // keys per sub-block (one 32-deep PV fragment)
+  constexpr int KF = HD / 32, DT = HD / 16, NC = HD / 8;
+  constexpr int BLK = SB * HD * 2;             // bytes of one K (or V) sub-block
+  constexpr int PPW = BLK / 1024;              // 1 KiB DMA pieces per V sub-block
+  constexpr int RPP = 1024 / (HD * 2);         // rows per piece
+  constexpr int NKL = 2 * KF;                  // K fragment loads per lane and sub-block
+  constexpr int WREG = 2 * BLK;                // one wave's staging: [buffer] V only
+  constexpr int MERGE = NW * (16 * HD + 32) * 4;
+  constexpr int SMEM = NW * WREG > MERGE ? NW * WREG : MERGE;
+  constexpr int SPP = KVP_PAGE / SB;           // sub-blocks per page
+  constexpr int WIN = LSA_WAVE * SPP;          // sub-blocks per table window (one entry per lane)
+  static_assert(PPW >= 1, "geometry");
+  static_assert(KVP_PAGE % SB == 0, "a sub-block lies in one page");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
+
+  const int row = blockIdx.x / n_kv, kvh = blockIdx.x % n_kv;
+  const int G = n_heads / n_kv;
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l16 = lane & 15;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slot = dslot[row];
+  int kl = dkvlen ? dkvlen[row] : dpos[row] + 1;
+  kl = kl < t_max ? kl : t_max;  // never read past the table row
+  const bool col_ok = l16 < G;   // MFMA column l16 = query head kvh * G + l16
+
+  // Q^T fragments (B operand): lane holds Q[head l16][kf*32 + 8g .. +7]
+  u32x4_t qf[KF];
+  {
+    const bf16_raw* qrow = q + (size_t)row * ldq + (size_t)(kvh * G + (col_ok ? l16 : 0)) * HD;
+#pragma unroll
+    for (int kf = 0; kf < KF; ++kf) qf[kf] = col_ok ? ld16(qrow + kf * 32 + g * 8) : u32x4_t{0u, 0u, 0u, 0u};
+  }
+  const int npg_row = t_max / KVP_PAGE;                     // entries of one table row
+  const int* tb = table + (size_t)slot * npg_row;           // the slot's table row
+  const size_t hstride = (size_t)KVP_PAGE * HD;             // elements of one (page, kv-head) run
+  unsigned char* my = smem + w * WREG;
+  int tw = 0, twin = -1;  // this lane's entry of table window twin (none loaded yet)
+
+  // Sub-block sb: its page from the window (no load), then V by LDS-DMA into this wave's buffer
+  // `buf` and K straight into registers, exactly the static kernel's operations on the page's run.
+  // A key past the length is clamped to kl - 1, which lies in this sub-block (sb < nsb), hence in
+  // this page: no cell at or beyond the length and no other page is touched.
+  auto stage = [&](int sb, int buf, u32x4_t (&kr)[2][KF]) {
+    const int win = sb / WIN;
+    if (win != twin) {
+      const int i = win * LSA_WAVE + lane;
+      tw = i < npg_row ? tb[i] : 0;
+      // the load retires here, inside the branch: past the join no load is pending on tw, so the
+      // readlane below costs no vmcnt wait on the trips that kept their window
+      asm volatile("" : "+v"(tw));
+      twin = win;
+    }
+    const int e = __builtin_amdgcn_readlane(tw, (sb / SPP) % LSA_WAVE);
+    const size_t run = ((size_t)page_of(e, n_pages) * n_kv + kvh) * hstride;
+    // the (page, kv-head) run: 64-bit and wave-uniform; inside it a lane's byte offset is < 16 KiB
+    const unsigned char* kb_ptr = reinterpret_cast<const unsigned char*>(kp + run);
+    const unsigned char* vb_ptr = reinterpret_cast<const unsigned char*>(vp + run);
+    const int t0 = (sb % SPP) * SB;           // the sub-block's first key inside the page
+    const int last = kl - 1 - sb / SPP * KVP_PAGE;  // kl - 1 inside the page (>= t0)
+    unsigned char* vd = my + buf * BLK;
+#pragma unroll
+    for (int s = 0; s < PPW; ++s) {
+      const int r = s * RPP + lane / NC, cs = lane % NC;
+      const int ch = cs ^ kvm_swz<HD>(r);
+      const unsigned key = (unsigned)min(t0 + r, last);  // clamped rows are masked in the softmax
+      kvm_glds16_nt(vb_ptr + (key * (HD * 2) + ch * 16), vd + s * 1024);
+    }
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+      const unsigned key = (unsigned)min(t0 + kt * 16 + l16, last);
+#pragma unroll
+      for (int kf = 0; kf < KF; ++kf) kr[kt][kf] = ld16_nt(kb_ptr + (key * (HD * 2) + g * 16) + kf * 64);
+    }
+  };
+
+  float o[DT][4];
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[d][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  int v_off[DT];
+  const int key_lo = 4 * g + (l16 >> 2);
+#pragma unroll
+  for (int d = 0; d < DT; ++d) v_off[d] = kvm_sw_off<HD>(key_lo, 2 * d + ((l16 & 3) >> 1)) + 8 * (l16 & 1);
+
+  // one sub-block: K from registers kr, V from buffer buf
+  auto compute = [&](int sb, int buf, const u32x4_t (&kr)[2][KF]) {
+    const unsigned char* vs = my + buf * BLK;
+    f32x4_t s[2];
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+      s[kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kf = 0; kf < KF; ++kf) s[kt] = mfma16(kr[kt][kf], qf[kf], s[kt]);
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = sb * SB + kt * 16 + g * 4 + r;
+        const float v = key < kl ? s[kt][r] * scale_log2 : -INFINITY;
+        s[kt][r] = v;
+        mx = fmaxf(mx, v);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+    float psum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = __builtin_amdgcn_exp2f(s[kt][r] - m_use);
+        s[kt][r] = pv;
+        psum += pv;
+      }
+    l_run = l_run * alpha + psum;
+    if (__builtin_amdgcn_ballot_w64(m_new != m_run)) {
+      // (element by element: no packed FP32 multiply is formed from this)
+#pragma unroll
+      for (int d = 0; d < DT; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[d][r] *= alpha;
+    }
+    m_run = m_new;
+    float pf[8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pf[r] = s[0][r];
+      pf[4 + r] = s[1][r];
+    }
+    const u32x4_t b = pack8(pf);
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+      const kvm_v4s_t lo =
+          __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) kvm_v4s_t*)(vs + v_off[d]));
+      const kvm_v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) kvm_v4s_t*)(vs + 16 * (HD * 2) + v_off[d]));
+      u32x4_t a;
+      a[0] = __builtin_bit_cast(u32x2_t, lo)[0];
+      a[1] = __builtin_bit_cast(u32x2_t, lo)[1];
+      a[2] = __builtin_bit_cast(u32x2_t, hi)[0];
+      a[3] = __builtin_bit_cast(u32x2_t, hi)[1];
+      const f32x4_t acc = mfma16(a, b, f32x4_t{o[d][0], o[d][1], o[d][2], o[d][3]});
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[d][r] = acc[r];
+    }
+  };
+
+  // The static kernel's schedule: two register / LDS buffers alternate with compile-time indices;
+  // before reading sub-block sb the wave restages the other buffer with sb + NW and waits until only
+  // that later stage's PPW + NKL operations are in flight.
+  const int nsb = (kl + SB - 1) / SB;
+  u32x4_t k0r[2][KF], k1r[2][KF];
+  auto step = [&](int sb, int cur, u32x4_t (&kcur)[2][KF], u32x4_t (&knext)[2][KF]) {
+    if (sb + NW < nsb) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the other buffer's V reads retired
+      __builtin_amdgcn_sched_barrier(0);
+      stage(sb + NW, cur ^ 1, knext);
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PPW + NKL) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    compute(sb, cur, kcur);
+  };
+  int sb = w;
+  if (sb < nsb) stage(sb, 0, k0r);
+  for (; sb < nsb; sb += 2 * NW) {
+    step(sb, 0, k0r, k1r);
+    if (sb + NW >= nsb) break;
+    step(sb + NW, 1, k1r, k0r);
+  }
+  l_run += __shfl_xor(l_run, 16, 64);
+  l_run += __shfl_xor(l_run, 32, 64);
+
+  // merge the NW partial states through LDS: per wave O^T[dim][head] (fp32), m[head], l[head]
+  __syncthreads();  // every wave is done with its staging buffers
+  float* Ow = reinterpret_cast<float*>(smem);           // [NW][16 heads][HD]
+  float* mw = Ow + NW * 16 * HD;                          // [NW][16]
+  float* lw = mw + NW * 16;                               // [NW][16]
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Ow[(w * 16 + l16) * HD + d * 16 + 4 * g + r] = o[d][r];
+  if (g == 0) {
+    mw[w * 16 + l16] = m_run;
+    lw[w * 16 + l16] = l_run;
+  }
+  __syncthreads();
+  // 8 output dims per thread-unit: units (head < G, dim octet)
+  for (int u = tid; u < G * (HD / 8); u += NW * 64) {
+    const int hh = u / (HD / 8), d0 = (u % (HD / 8)) * 8;
+    float M = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) M = fmaxf(M, mw[i * 16 + hh]);
+    const float Mu = M == -INFINITY ? 0.f : M;
+    float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const float f = __builtin_amdgcn_exp2f(mw[i * 16 + hh] - Mu);
+      L += lw[i * 16 + hh] * f;
+      const float* src = Ow + (i * 16 + hh) * HD + d0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += src[j] * f;
+    }
+    const float inv = L > 0.f ? 1.f / L : 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] *= inv;
+    st16(out + (size_t)row * ldo + (size_t)(kvh * G + hh) * HD + d0, pack8(acc));
+  }
+}
+
+template <int HD>
+int launch_gqa_decode_paged(int nw, unsigned grid, const bf16_raw* q, int ldq, const bf16_raw* kp, const bf16_raw* vp,
+                            const int* table, int n_pages, const int* slot, const int* pos, const int* kvlen,
+                            int n_heads, int n_kv, int t_max, float sl2, bf16_raw* o, int ldo, hipStream_t stream) {
+  if (nw == 1)
+    gqa_decode_paged_kernel<HD, 1><<<grid, 64, 0, stream>>>(q, ldq, kp, vp, table, n_pages, slot, pos, kvlen, n_heads,
+                                                            n_kv, t_max, sl2, o, ldo);
+  else if (nw == 2)
+    gqa_decode_paged_kernel<HD, 2><<<grid, 128, 0, stream>>>(q, ldq, kp, vp, table, n_pages, slot, pos, kvlen, n_heads,
+                                                             n_kv, t_max, sl2, o, ldo);
+  else
+    gqa_decode_paged_kernel<HD, 4><<<grid, 256, 0, stream>>>(q, ldq, kp, vp, table, n_pages, slot, pos, kvlen, n_heads,
+                                                             n_kv, t_max, sl2, o, ldo);
+  LSA_CHECK_LAUNCH();
+  return LSA_OK;
+}
+
 }  // namespace
+
+// lsa_attn_decode_mfma (kernels/attn_prefill.hip) over pages: one workgroup per (row, kv-head), the
+// group's 2..16 query heads as the MFMA columns, keys [0, min(kv_len or pos + 1, t_max)) of the
+// row's slot read through its table row, split over ``nw`` = 1 / 2 / 4 waves (0 = 1). slot / pos /
+// kv_len / table are read on the device. The same bits as lsa_attn_decode_mfma on the static cache
+// the pages were cut from, for every nw. A refusal launches nothing.
+extern "C" int lsa_attn_decode_mfma_paged(const void* q, int ldq, const void* kp, const void* vp, const int* table,
+                                          int n_pages, const int* slot, const int* pos, const int* kv_len, int rows,
+                                          int n_heads, int n_kv, int head_dim, int t_max, float scale, void* out,
+                                          int ldo, int nw, hipStream_t stream) {
+  if (rows < 1 || n_kv < 1 || n_heads < 1 || n_heads % n_kv || !slot || !pos) return LSA_BAD_SHAPE;
+  if (!q || !kp || !vp || !table || !out) return LSA_BAD_SHAPE;
+  if (n_pages < 2 || t_max < KVP_PAGE || t_max % KVP_PAGE) return LSA_BAD_SHAPE;
+  const int g = n_heads / n_kv;
+  if (g < 2 || g > 16) return LSA_UNSUPPORTED;
+  if (head_dim != 128 && head_dim != 64) return LSA_UNSUPPORTED;
+  if (ldo % 8 || reinterpret_cast<uintptr_t>(out) % 16 || ldq % 8 || reinterpret_cast<uintptr_t>(q) % 16)
+    return LSA_BAD_SHAPE;
+  if (reinterpret_cast<uintptr_t>(kp) % 16 || reinterpret_cast<uintptr_t>(vp) % 16) return LSA_BAD_SHAPE;
+  if (nw == 0) nw = 1;
+  if (nw != 1 && nw != 2 && nw != 4) return LSA_UNSUPPORTED;
+  const long long grid = (long long)rows * n_kv;
+  if (grid >= (1ll << 31)) return LSA_BAD_SHAPE;
+  const float sl2 = scale * 1.4426950408889634f;
+  const auto* qq = static_cast<const bf16_raw*>(q);
+  const auto* k = static_cast<const bf16_raw*>(kp);
+  const auto* v = static_cast<const bf16_raw*>(vp);
+  auto* o = static_cast<bf16_raw*>(out);
+  return head_dim == 128 ? launch_gqa_decode_paged<128>(nw, (unsigned)grid, qq, ldq, k, v, table, n_pages, slot, pos,
+                                                        kv_len, n_heads, n_kv, t_max, sl2, o, ldo, stream)
+                         : launch_gqa_decode_paged<64>(nw, (unsigned)grid, qq, ldq, k, v, table, n_pages, slot, pos,
+                                                       kv_len, n_heads, n_kv, t_max, sl2, o, ldo, stream);
+}
 
 // lsa_attn_decode over pages. small_max_wgs: rows * n_kv at or below which a one-split launch takes
 // the 8-wave one-trip kernel (the value lsa_attn_set_small_max_wgs holds for the static kernel; 128).

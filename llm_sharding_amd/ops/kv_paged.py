@@ -178,7 +178,10 @@ def _lib():
                                             vp, vp]
         L.lsa_kvp_append.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.lsa_kvp_gather.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
-        for name in ("lsa_attn_decode_paged", "lsa_kvp_append", "lsa_kvp_gather"):
+        if not hasattr(L, "lsa_attn_decode_mfma_paged"):
+            raise RuntimeError("the kernel library has no lsa_attn_decode_mfma_paged: rebuild it (python csrc/build.py)")
+        L.lsa_attn_decode_mfma_paged.argtypes = [vp, i, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, f, vp, i, i, vp]
+        for name in ("lsa_attn_decode_paged", "lsa_attn_decode_mfma_paged", "lsa_kvp_append", "lsa_kvp_gather"):
             getattr(L, name).restype = i
         _L = L
     return _L
@@ -247,30 +250,65 @@ def kvp_gather(kp: torch.Tensor, vp: torch.Tensor, table: torch.Tensor, k_stage:
     _check(rc, "lsa_kvp_gather")
 
 
+def _check_attn(q, kp, vp, table, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, what: str) -> tuple:
+    """The tensor checks both decode attentions share; returns the pool's shape."""
+    hip._req(table is not None, f"{what}: a block table")
+    shape = _check_dev_pool(kp, vp, table, what)
+    hip._req(hip._is_bf16_cuda(q, out), f"{what}: bf16 cuda q / out")
+    hip._req(shape[1] == n_kv and shape[3] == head_dim, f"{what}: page dims")
+    hip._req(n_kv >= 1 and n_heads >= 1 and n_heads % n_kv == 0, f"{what}: GQA group {n_heads}/{n_kv}")
+    hip._req(rows >= 1 and q.dim() == 2 and q.shape[0] >= rows and q.shape[1] >= n_heads * head_dim
+             and q.stride(1) == 1 and q.stride(0) % 8 == 0, f"{what}: q shape")
+    hip._req(out.dim() == 2 and out.shape[0] >= rows and out.shape[1] >= n_heads * head_dim and out.stride(1) == 1,
+             f"{what}: out shape")
+    hip._req(slot.is_cuda and pos.is_cuda and slot.dtype == torch.int32 and pos.dtype == torch.int32
+             and slot.numel() >= rows and pos.numel() >= rows, f"{what}: int32 cuda slot/pos")
+    hip._req(kv_len is None or (kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.numel() >= rows),
+             f"{what}: int32 cuda kv_len")
+    return shape
+
+
+def attn_paged_mfma(q: torch.Tensor, kp: torch.Tensor, vp: torch.Tensor, table: torch.Tensor, slot: torch.Tensor,
+                    pos: torch.Tensor, rows: int, n_heads: int, n_kv: int, head_dim: int, out: torch.Tensor,
+                    kv_len: Optional[torch.Tensor] = None, scale: Optional[float] = None, nw: int = 0) -> None:
+    """``lsa_attn_decode_mfma`` over pages (csrc/cache/kv_paged.hip): GQA decode attention with the
+    group's 2..16 query heads as the MFMA columns, one workgroup per (row, kv-head), no split over
+    workgroups, ``nw`` = 1 / 2 / 4 waves per item (0 = 1). Row ``m`` attends keys
+    ``[0, kv_len[m] or pos[m] + 1)`` of slot ``slot[m]`` through its table row. The same bits as
+    ``lsa_attn_decode_mfma`` on the static cache the pages were cut from, for every ``nw``."""
+    shape = _check_attn(q, kp, vp, table, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, "attn_paged_mfma")
+    hip._req(2 <= n_heads // n_kv <= 16, f"attn_paged_mfma: GQA group {n_heads}/{n_kv} outside 2..16")
+    hip._req(nw in (0, 1, 2, 4), "attn_paged_mfma: nw 0 / 1 / 2 / 4")
+    hip._req(out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0,
+             "attn_paged_mfma: 16-byte aligned q / out rows")
+    sc = head_dim ** -0.5 if scale is None else scale
+    rc = _lib().lsa_attn_decode_mfma_paged(hip._p(q), q.stride(0), hip._p(kp), hip._p(vp), hip._p(table), shape[0],
+                                           hip._p(slot), hip._p(pos), hip._p(kv_len), rows, n_heads, n_kv, head_dim,
+                                           table.shape[1] * PAGE, float(sc), hip._p(out), out.stride(0), int(nw),
+                                           hip._stream())
+    _check(rc, "lsa_attn_decode_mfma_paged")
+
+
 def attn_paged(q: torch.Tensor, kp: torch.Tensor, vp: torch.Tensor, table: torch.Tensor, slot: torch.Tensor,
                pos: torch.Tensor, rows: int, n_heads: int, n_kv: int, head_dim: int, nsplit: int,
                part_o: Optional[torch.Tensor], part_lse: Optional[torch.Tensor], out: torch.Tensor,
                kv_len: Optional[torch.Tensor] = None, min_chunk: int = 64, scale: Optional[float] = None,
                counters: Optional[torch.Tensor] = None) -> None:
-    """``lsa_attn_decode`` over pages (csrc/cache/kv_paged.hip): :func:`hip.attn`'s arguments and
-    semantics with (kp, vp, table) in place of the static caches, and always the split-KV VALU
-    kernels (never the MFMA GQA kernel, which does not read pages). ``counters``: >= rows * n_kv
-    zeroed int32, left zeroed (default: the stream's coop workspace)."""
-    hip._req(table is not None, "attn_paged: a block table")
-    shape = _check_dev_pool(kp, vp, table, "attn_paged")
-    hip._req(hip._is_bf16_cuda(q, out), "attn_paged: bf16 cuda q / out")
-    hip._req(shape[1] == n_kv and shape[3] == head_dim, "attn_paged: page dims")
-    hip._req(n_kv >= 1 and n_heads % n_kv == 0 and (n_heads // n_kv) in KVP_GROUPS,
-             f"attn_paged: GQA group {n_heads}/{n_kv} not built {KVP_GROUPS}")
-    hip._req(rows >= 1 and q.dim() == 2 and q.shape[0] >= rows and q.shape[1] >= n_heads * head_dim
-             and q.stride(1) == 1 and q.stride(0) % 8 == 0, "attn_paged: q shape")
-    hip._req(out.dim() == 2 and out.shape[0] >= rows and out.shape[1] >= n_heads * head_dim and out.stride(1) == 1,
-             "attn_paged: out shape")
+    """Decode attention over pages (csrc/cache/kv_paged.hip): :func:`hip.attn`'s arguments,
+    semantics and kernel choice with (kp, vp, table) in place of the static caches. A GQA batch
+    (group 2..16) of ``hip.ATTN_MFMA_MIN_ITEMS`` or more (row, kv-head) items goes to
+    :func:`attn_paged_mfma` with ``hip.ATTN_GQA_NW`` waves while ``hip.ATTN_MFMA`` is set (the three
+    are read at call time, as hip.attn reads them); everything else takes ``lsa_attn_decode_paged``,
+    the split-KV VALU kernels. Either way the bits are those of hip.attn on the static cache the
+    pages were cut from. ``counters``: >= rows * n_kv zeroed int32, left zeroed (default: the
+    stream's coop workspace)."""
+    if hip.ATTN_MFMA and n_kv >= 1 and 2 <= n_heads // n_kv <= 16 and rows * n_kv >= hip.ATTN_MFMA_MIN_ITEMS:
+        attn_paged_mfma(q, kp, vp, table, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len=kv_len, scale=scale,
+                        nw=hip.ATTN_GQA_NW)
+        return
+    shape = _check_attn(q, kp, vp, table, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, "attn_paged")
+    hip._req((n_heads // n_kv) in KVP_GROUPS, f"attn_paged: GQA group {n_heads}/{n_kv} not built {KVP_GROUPS}")
     hip._req(1 <= nsplit <= KVP_MAX_SPLIT and min_chunk >= 1, "attn_paged: nsplit 1..16, min_chunk >= 1")
-    hip._req(slot.is_cuda and pos.is_cuda and slot.dtype == torch.int32 and pos.dtype == torch.int32
-             and slot.numel() >= rows and pos.numel() >= rows, "attn_paged: int32 cuda slot/pos")
-    hip._req(kv_len is None or (kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.numel() >= rows),
-             "attn_paged: int32 cuda kv_len")
     if nsplit > 1:
         hip._req(part_o is not None and part_lse is not None and part_o.dtype == torch.float32
                  and part_lse.dtype == torch.float32 and part_o.numel() >= rows * n_heads * nsplit * head_dim

@@ -10,10 +10,10 @@ runtime/engine_kv8.py): ``k_cache[li]`` / ``v_cache[li]`` are that pair for ever
 projection route and every EPI_QKV epilogue runs unchanged. Then, per layer:
 
 * ``lsa_kvp_append`` copies the step's cells from the staging layer into their pages;
-* decode rows (every forward without a tile table) attend the pages with ``lsa_attn_decode_paged``,
-  always the split-KV kernels: where ``hip.attn`` would take the MFMA GQA kernel (a GQA model at
-  512 or more (row, kv-head) items) the paged engine does not, so bitwise equality with the bf16
-  engine holds for group 1 or fewer than 512 items;
+* decode rows (every forward without a tile table) attend the pages through ``kv_paged.attn``,
+  which takes ``hip.attn``'s decision: ``lsa_attn_decode_mfma_paged`` for a GQA model at 512 or
+  more (row, kv-head) items, ``lsa_attn_decode_paged`` (the split-KV kernels) otherwise - each the
+  bits of its static twin, so bitwise equality with the bf16 engine holds on every route;
 * a flash-prefill forward first gathers ``[0, p0)`` of every slot whose tiles start at ``p0 > 0``
   back into the staging layer (``lsa_kvp_gather``) and then runs ``hip.attn_prefill`` unchanged.
 

@@ -6,9 +6,14 @@
   allocation order and shuffled over the pool. A batch-1 window is one graph of 512 launches over 512 distinct
   slots (beyond the 256 MB Infinity Cache), so that every launch streams cold K/V; the larger shapes stream
   1 GB or more per launch. lsa_kvp_append at 1 / 128 / 512 rows, lsa_kvp_gather of a 2048-token prefix.
+  Then the GQA lines (--gqa runs them alone): lsa_attn_decode_mfma_paged at 70B heads (64 / 8) and 3B heads
+  (24 / 8), hd 128, 512 rows x 150 and 2048 keys, pages in order and shuffled, against lsa_attn_decode_mfma on
+  the static cache and lsa_attn_decode_paged on the same pages.
   Alternating windows in one process; median and (max - min) / median.
 --steps: ms per decode step of random-init llama2-7b at 512 sequences and at batch 1, one captured decode
-  graph per layout on ~143 tokens of context, the two alternated window by window.
+  graph per layout on ~143 tokens of context, the two alternated window by window. For a GQA model
+  (--model llama3.2-3b) a third graph, paged_split, is the paged engine captured with the MFMA route off: the
+  split-KV kernels at every batch, which is what the engine launched before lsa_attn_decode_mfma_paged.
 --serve: serve.py's load test (child processes, one after the other) at max_seq 4096 with 128 + 128-token
   requests, two micro-batches: the static cache at 2 x 61 slots (what ``--batch 0`` sizes for a 288 GB
   device), the paged cache at 2 x 256 slots with ``--kv-pages 0``; tokens/s, p50 TPOT and the peak of requests
@@ -127,6 +132,60 @@ def kernels(windows: int, out: list) -> None:
         torch.cuda.empty_cache()
 
 
+def gqa_kernels(windows: int, out: list) -> None:
+    """lsa_attn_decode_mfma_paged against lsa_attn_decode_mfma on the static cache and against
+    lsa_attn_decode_paged (one split, as the engine picks at 4096 items) on the same pages."""
+    rows, hd = 512, HD
+    for nh, nkv in ((64, 8), (24, 8)):
+        for ctx in (150, 2048):
+            T = -(-(ctx + 1) // PAGE) * PAGE
+            kc = torch.empty(rows, nkv, T, hd, dtype=torch.bfloat16, device=DEV)
+            vc = torch.empty_like(kc)
+            n_pages = rows * (T // PAGE) + 1
+            kp = torch.empty(n_pages, nkv, PAGE, hd, dtype=torch.bfloat16, device=DEV)
+            vp = torch.empty_like(kp)
+            for t in (kc, vc, kp, vp):
+                _fill(t)
+            tabs = _tables(rows, T // PAGE)
+            q = torch.randn(rows, nh * hd, device=DEV).to(torch.bfloat16)
+            o = torch.zeros(rows, nh * hd, dtype=torch.bfloat16, device=DEV)
+            pos = torch.full((rows,), ctx - 1, dtype=torch.int32, device=DEV)
+            sl = torch.arange(rows, dtype=torch.int32, device=DEV)
+            L, p = hip.lib(), hip._p
+
+            def static(i):
+                rc = L.lsa_attn_decode_mfma(p(q), q.stride(0), p(kc), p(vc), p(sl), p(pos), None, rows, nh, nkv, hd, T,
+                                            float(hd ** -0.5), p(o), o.stride(0), hip.ATTN_GQA_NW, hip._stream())
+                assert rc == 0
+
+            def mfma(tab):
+                return lambda i: kv_paged.attn_paged_mfma(q, kp, vp, tab, sl, pos, rows, nh, nkv, hd, o, nw=hip.ATTN_GQA_NW)
+
+            def split(i):  # the route the paged engine took before: the VALU kernel, one split
+                prev, hip.ATTN_MFMA = hip.ATTN_MFMA, False
+                try:
+                    kv_paged.attn_paged(q, kp, vp, tabs["shuffled"], sl, pos, rows, nh, nkv, hd, 1, None, None, o,
+                                        min_chunk=256)
+                finally:
+                    hip.ATTN_MFMA = prev
+            fns = {"static_mfma": static, "paged_mfma_order": mfma(tabs["order"]),
+                   "paged_mfma_shuffled": mfma(tabs["shuffled"]), "paged_split_shuffled": split}
+            r = _windows(fns, windows)
+            nbytes = rows * nkv * ctx * 2 * hd * 2
+            line = {"kind": "attn_gqa", "rows": rows, "n_heads": nh, "n_kv": nkv, "hd": hd, "context": ctx,
+                    "nw": hip.ATTN_GQA_NW or 1, "bytes": nbytes, "windows": windows}
+            for k, (us, spread) in r.items():
+                line[k + "_us"], line[k + "_spread"] = round(us, 2), round(spread, 3)
+                line[k + "_TBps"] = round(nbytes / us / 1e6, 3)
+            for k in ("paged_mfma_order", "paged_mfma_shuffled"):
+                line[k + "_vs_static_mfma"] = round(r[k][0] / r["static_mfma"][0], 4)
+            line["paged_split_vs_paged_mfma"] = round(r["paged_split_shuffled"][0] / r["paged_mfma_shuffled"][0], 4)
+            print(json.dumps(line), flush=True)
+            out.append(line)
+            del kc, vc, kp, vp
+            torch.cuda.empty_cache()
+
+
 def _engine(cfg, layout, slots, max_seq, rows):
     from llm_sharding_amd.runtime.engine import RandomSource
     from llm_sharding_amd.runtime.engine_int4 import make_stage_engine
@@ -140,6 +199,7 @@ def steps(model: str, batches, windows: int, n_steps: int, ctx: int, out: list) 
     from llm_sharding_amd.runtime.engine import DecodeGraph
     cfg = get_preset(model)
     B = max(batches)
+    gqa = cfg.num_attention_heads // cfg.num_key_value_heads >= 2
     graphs = {}
     max_seq = -(-(ctx + n_steps + 2) // PAGE) * PAGE
     for layout in ("static", "paged"):
@@ -154,6 +214,14 @@ def steps(model: str, batches, windows: int, n_steps: int, ctx: int, out: list) 
             e.seq_len[s] = ctx - n_steps // 2  # the timed steps straddle the context length
         for b in batches:
             graphs[(layout, b)] = DecodeGraph(e, b, "full", slots=list(range(b))).capture()
+            if layout == "paged" and gqa:
+                # the paged engine's route before lsa_attn_decode_mfma_paged: the split-KV kernels for
+                # every batch (captured with the MFMA route switched off; those kernels did not change)
+                prev, hip.ATTN_MFMA = hip.ATTN_MFMA, False
+                try:
+                    graphs[("paged_split", b)] = DecodeGraph(e, b, "full", slots=list(range(b))).capture()
+                finally:
+                    hip.ATTN_MFMA = prev
         print(json.dumps({"loaded": layout, "engine": type(e).__name__,
                           "weights_plus_kv_GB": round(e.memory_bytes() / 1e9, 2)}), flush=True)
 
@@ -170,7 +238,7 @@ def steps(model: str, batches, windows: int, n_steps: int, ctx: int, out: list) 
         return a.elapsed_time(b) / n_steps
 
     for b in batches:
-        t = {layout: [] for layout in ("static", "paged")}
+        t = {layout: [] for layout in ("static", "paged") + (("paged_split",) if gqa else ())}
         for _ in range(windows):
             for layout in t:
                 t[layout].append(run(graphs[(layout, b)]))
@@ -179,6 +247,8 @@ def steps(model: str, batches, windows: int, n_steps: int, ctx: int, out: list) 
             line[layout + "_ms"] = round(statistics.median(v), 4)
             line[layout + "_spread"] = round((max(v) - min(v)) / statistics.median(v), 3)
         line["paged_vs_static"] = round(line["paged_ms"] / line["static_ms"], 4)
+        if gqa:
+            line["paged_vs_paged_split"] = round(line["paged_ms"] / line["paged_split_ms"], 4)
         print(json.dumps(line), flush=True)
         out.append(line)
 
@@ -204,7 +274,7 @@ def serve(model: str, requests: int, timeout_s: int, out: list) -> None:
 
 def main():
     ap = argparse.ArgumentParser()
-    for flag in ("--kernels", "--steps", "--serve"):
+    for flag in ("--kernels", "--gqa", "--steps", "--serve"):
         ap.add_argument(flag, action="store_true")
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--batches", default="512,1")
@@ -219,6 +289,8 @@ def main():
     out = []
     if a.kernels:
         kernels(a.windows, out)
+    if a.kernels or a.gqa:
+        gqa_kernels(a.windows, out)
     if a.steps:
         steps(a.model, [int(b) for b in a.batches.split(",")], a.windows, a.n_steps, a.context, out)
     if a.serve:
