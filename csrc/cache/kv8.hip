@@ -5,6 +5,8 @@
 //   lsa_kv8_dequant       codes + scales of [0, len) of the named slots -> the bf16 staging layer
 //   lsa_attn_decode_kv8   lsa_attn_decode (kernels/attention.hip, attn_body.h) over k8 / v8 / ks / vs
 //   lsa_attn_kv8_kpi      keys per workgroup iteration of the kernel a shape launches (chunk edges)
+//   (lsa_attn_decode_mfma_kv8, the GQA decode on MFMA over the same tensors for batches of many
+//    (row, kv-head) items, lives in kv8_mfma.hip; ops/kv8.py attn chooses between the two)
 //
 // Format (ops/kv8.py states it in torch). One layer holds k8, v8: uint8 [slots, n_kv, t_max, hd] and
 // ks, vs: fp32 [slots, n_kv, t_max]. For a vector x of hd finite bf16 values: a = max |x_d|;

@@ -1,5 +1,5 @@
 """FP8 KV cache (kv_dtype="fp8"): the format, its torch references and the bindings of
-csrc/cache/kv8.hip.
+csrc/cache/kv8.hip and csrc/cache/kv8_mfma.hip (the GQA decode attention on MFMA).
 
 A layer's cache is four tensors: ``k8`` / ``v8`` uint8 ``[slots, n_kv, max_seq, hd]`` holding OCP
 e4m3fn codes and ``ks`` / ``vs`` fp32 ``[slots, n_kv, max_seq]``, one scale per cached vector (the
@@ -101,7 +101,11 @@ def _lib():
         L.lsa_kv8_append.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.lsa_kv8_dequant.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.lsa_attn_kv8_kpi.argtypes = [i]
-        for name in ("lsa_attn_decode_kv8", "lsa_kv8_append", "lsa_kv8_dequant", "lsa_attn_kv8_kpi"):
+        if not hasattr(L, "lsa_attn_decode_mfma_kv8"):
+            raise RuntimeError("the kernel library has no lsa_attn_decode_mfma_kv8: rebuild it (python csrc/build.py)")
+        L.lsa_attn_decode_mfma_kv8.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, i, i, vp]
+        for name in ("lsa_attn_decode_kv8", "lsa_attn_decode_mfma_kv8", "lsa_kv8_append", "lsa_kv8_dequant",
+                     "lsa_attn_kv8_kpi"):
             getattr(L, name).restype = i
         _L = L
     return _L
@@ -158,28 +162,35 @@ def kv8_dequant(k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.
     hip._check(rc, "lsa_kv8_dequant")
 
 
+def _check_attn(q, k8, v8, ks, vs, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, what: str) -> tuple:
+    """The tensor checks both decode attentions share; returns the cache's shape."""
+    shape = _check_cache(k8, v8, ks, vs, what)
+    hip._req(hip._is_bf16_cuda(q, out), f"{what}: bf16 cuda q / out")
+    hip._req(shape[1] == n_kv and shape[3] == head_dim, f"{what}: cache dims")
+    hip._req(n_kv >= 1 and n_heads >= 1 and n_heads % n_kv == 0, f"{what}: GQA group {n_heads}/{n_kv}")
+    hip._req(rows >= 1 and q.dim() == 2 and q.shape[0] >= rows and q.shape[1] >= n_heads * head_dim
+             and q.stride(1) == 1 and q.stride(0) % 8 == 0, f"{what}: q shape")
+    hip._req(out.dim() == 2 and out.shape[0] >= rows and out.shape[1] >= n_heads * head_dim and out.stride(1) == 1,
+             f"{what}: out shape")
+    hip._req(slot.is_cuda and pos.is_cuda and slot.dtype == torch.int32 and pos.dtype == torch.int32
+             and slot.numel() >= rows and pos.numel() >= rows, f"{what}: int32 cuda slot/pos")
+    hip._req(kv_len is None or (kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.numel() >= rows),
+             f"{what}: int32 cuda kv_len")
+    return shape
+
+
 def attn_kv8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
              slot: torch.Tensor, pos: torch.Tensor, rows: int, n_heads: int, n_kv: int, head_dim: int, nsplit: int,
              part_o: Optional[torch.Tensor], part_lse: Optional[torch.Tensor], out: torch.Tensor,
              kv_len: Optional[torch.Tensor] = None, min_chunk: int = 64, scale: Optional[float] = None,
              counters: Optional[torch.Tensor] = None) -> None:
-    """:func:`hip.attn` over an fp8 cache (csrc/cache/kv8.hip): same arguments and semantics, with
-    (k8, v8, ks, vs) in place of the bf16 caches. ``counters``: >= rows * n_kv zeroed int32, left
-    zeroed (default: the stream's coop workspace); the partial buffers are needed for nsplit > 1."""
-    shape = _check_cache(k8, v8, ks, vs, "attn_kv8")
-    hip._req(hip._is_bf16_cuda(q, out), "attn_kv8: bf16 cuda q / out")
-    hip._req(shape[1] == n_kv and shape[3] == head_dim, "attn_kv8: cache dims")
-    hip._req(n_kv >= 1 and n_heads % n_kv == 0 and (n_heads // n_kv) in KV8_GROUPS,
-             f"attn_kv8: GQA group {n_heads}/{n_kv} not built {KV8_GROUPS}")
-    hip._req(rows >= 1 and q.dim() == 2 and q.shape[0] >= rows and q.shape[1] >= n_heads * head_dim
-             and q.stride(1) == 1 and q.stride(0) % 8 == 0, "attn_kv8: q shape")
-    hip._req(out.dim() == 2 and out.shape[0] >= rows and out.shape[1] >= n_heads * head_dim and out.stride(1) == 1,
-             "attn_kv8: out shape")
+    """:func:`hip.attn`'s split-KV kernel over an fp8 cache (csrc/cache/kv8.hip): same arguments and
+    semantics, with (k8, v8, ks, vs) in place of the bf16 caches. ``counters``: >= rows * n_kv zeroed
+    int32, left zeroed (default: the stream's coop workspace); the partial buffers are needed for
+    nsplit > 1."""
+    shape = _check_attn(q, k8, v8, ks, vs, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, "attn_kv8")
+    hip._req((n_heads // n_kv) in KV8_GROUPS, f"attn_kv8: GQA group {n_heads}/{n_kv} not built {KV8_GROUPS}")
     hip._req(1 <= nsplit <= KV8_MAX_SPLIT and min_chunk >= 1, "attn_kv8: nsplit 1..16, min_chunk >= 1")
-    hip._req(slot.is_cuda and pos.is_cuda and slot.dtype == torch.int32 and pos.dtype == torch.int32
-             and slot.numel() >= rows and pos.numel() >= rows, "attn_kv8: int32 cuda slot/pos")
-    hip._req(kv_len is None or (kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.numel() >= rows),
-             "attn_kv8: int32 cuda kv_len")
     if nsplit > 1:
         hip._req(part_o is not None and part_lse is not None and part_o.dtype == torch.float32
                  and part_lse.dtype == torch.float32 and part_o.numel() >= rows * n_heads * nsplit * head_dim
@@ -195,7 +206,54 @@ def attn_kv8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tens
     hip._check(rc, "lsa_attn_decode_kv8")
 
 
-attn = attn_kv8  # (the engine's call reads as hip.attn's: runtime/engine_kv8.py)
+def mfma_serves(t_max: int) -> bool:
+    """Whether :func:`attn_kv8_mfma` takes a cache of ``t_max`` positions: its 16-byte loads of four
+    keys' scales need ``t_max`` to be a multiple of 4."""
+    return t_max >= 4 and t_max % 4 == 0
+
+
+def attn_kv8_mfma(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                  slot: torch.Tensor, pos: torch.Tensor, rows: int, n_heads: int, n_kv: int, head_dim: int,
+                  out: torch.Tensor, kv_len: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                  nw: int = 0) -> None:
+    """``lsa_attn_decode_mfma`` over an fp8 cache (csrc/cache/kv8_mfma.hip): GQA decode attention with
+    the group's 2..16 query heads as the MFMA columns, one workgroup per (row, kv-head), no split over
+    workgroups, ``nw`` = 1 / 2 / 4 waves per item (0 = 1). Row ``m`` attends keys
+    ``[0, min(kv_len[m] or pos[m] + 1, max_seq))`` of slot ``slot[m]``; the codes are converted in
+    registers, ``ks`` scales the scores and ``vs`` is folded into P (:func:`attn_decode_reference`).
+    Refused (ValueError): groups outside 2..16, ``max_seq`` not a multiple of 4."""
+    shape = _check_attn(q, k8, v8, ks, vs, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len, "attn_kv8_mfma")
+    hip._req(2 <= n_heads // n_kv <= 16, f"attn_kv8_mfma: GQA group {n_heads}/{n_kv} outside 2..16")
+    hip._req(nw in (0, 1, 2, 4), "attn_kv8_mfma: nw 0 / 1 / 2 / 4")
+    hip._req(mfma_serves(shape[2]), f"attn_kv8_mfma: max_seq {shape[2]} is not a multiple of 4")
+    hip._req(out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0,
+             "attn_kv8_mfma: 16-byte aligned q / out rows")
+    hip._req(all(t.data_ptr() % 16 == 0 for t in (k8, v8, ks, vs)), "attn_kv8_mfma: 16-byte aligned cache tensors")
+    sc = head_dim ** -0.5 if scale is None else scale
+    rc = _lib().lsa_attn_decode_mfma_kv8(hip._p(q), q.stride(0), hip._p(k8), hip._p(v8), hip._p(ks), hip._p(vs),
+                                         hip._p(slot), hip._p(pos), hip._p(kv_len), rows, n_heads, n_kv, head_dim,
+                                         shape[2], float(sc), hip._p(out), out.stride(0), int(nw), hip._stream())
+    hip._check(rc, "lsa_attn_decode_mfma_kv8")
+
+
+def attn(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+         slot: torch.Tensor, pos: torch.Tensor, rows: int, n_heads: int, n_kv: int, head_dim: int, nsplit: int,
+         part_o: Optional[torch.Tensor], part_lse: Optional[torch.Tensor], out: torch.Tensor,
+         kv_len: Optional[torch.Tensor] = None, min_chunk: int = 64, scale: Optional[float] = None,
+         counters: Optional[torch.Tensor] = None) -> None:
+    """Decode attention over an fp8 cache with :func:`hip.attn`'s kernel choice (the engine's call
+    reads as hip.attn's: runtime/engine_kv8.py). A GQA batch (group 2..16) of
+    ``hip.ATTN_MFMA_MIN_ITEMS`` or more (row, kv-head) items goes to :func:`attn_kv8_mfma` with
+    ``hip.ATTN_GQA_NW`` waves while ``hip.ATTN_MFMA`` is set (the three are read at call time, as
+    hip.attn reads them) and ignores the split workspace; everything else - fewer items, group 1, the
+    switch off, a ``max_seq`` that is no multiple of 4 - takes :func:`attn_kv8` exactly as before."""
+    if (hip.ATTN_MFMA and n_kv >= 1 and 2 <= n_heads // n_kv <= 16 and rows * n_kv >= hip.ATTN_MFMA_MIN_ITEMS
+            and k8.dim() == 4 and mfma_serves(k8.shape[2])):
+        attn_kv8_mfma(q, k8, v8, ks, vs, slot, pos, rows, n_heads, n_kv, head_dim, out, kv_len=kv_len, scale=scale,
+                      nw=hip.ATTN_GQA_NW)
+        return
+    attn_kv8(q, k8, v8, ks, vs, slot, pos, rows, n_heads, n_kv, head_dim, nsplit, part_o, part_lse, out, kv_len=kv_len,
+             min_chunk=min_chunk, scale=scale, counters=counters)
 
 
 def attn_kv8_kpi(head_dim: int) -> int:

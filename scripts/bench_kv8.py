@@ -13,6 +13,10 @@
 --quality: logits rel_err and greedy-token agreement over 64 teacher-forced steps, the fp8-KV engine
   against the bf16 engine on the same random-init weights; the same two figures for fp8 WEIGHTS
   (bf16 KV) as a yardstick of what a random-init 32-layer model does to a small perturbation.
+--gqa: lsa_attn_decode_mfma_kv8 (1 / 2 / 4 waves) at 512 rows x 143 and 2048 tokens for the 24/8/128 and 64/8/128
+  shapes against lsa_attn_decode_kv8 at the engine's nsplit and against lsa_attn_decode_mfma on a bf16 cache of the
+  same shape; successive launches rotate over enough copies of the slots that the K/V read exceeds 600 MB, i.e. is
+  cold. Then ms per captured 512-sequence llama3.2-3b step with kv_dtype="fp8", the MFMA route on and off.
 One JSON line per result; everything is also written to --out."""
 import argparse
 import json
@@ -149,6 +153,90 @@ def steps(model: str, batches, windows: int, n_steps: int, ctx: int, out: list) 
         out.append(line)
 
 
+def gqa(windows: int, n_steps: int, out: list) -> None:
+    from llm_sharding_amd.config import get_preset
+    from llm_sharding_amd.runtime.engine import DecodeGraph
+    rows = 512
+    for nh, nkv, hd in ((24, 8, 128), (64, 8, 128)):
+        for ctx in (143, 2048):
+            T = -(-(ctx + 1) // 64) * 64
+            b8, b16 = rows * nkv * ctx * (2 * hd + 8), rows * nkv * ctx * 2 * hd * 2
+            copies = -(-600_000_000 // b8)
+            slots = rows * copies
+            rnd8 = lambda sh: torch.randint(0, 0x78, sh, device=DEV, dtype=torch.uint8) | \
+                (torch.randint(0, 2, sh, device=DEV, dtype=torch.uint8) << 7)
+            k8, v8 = (torch.empty(slots, nkv, T, hd, dtype=torch.uint8, device=DEV) for _ in range(2))
+            kc, vc = (torch.empty(slots, nkv, T, hd, dtype=torch.bfloat16, device=DEV) for _ in range(2))
+            for t in (k8, v8):
+                _fill(t, rnd8)
+            for t in (kc, vc):
+                _fill(t, lambda sh: torch.randn(sh, device=DEV).to(torch.bfloat16))
+            ks, vs = (torch.full((slots, nkv, T), 2.0 ** -6, device=DEV) for _ in range(2))
+            q = torch.randn(rows, nh * hd, device=DEV).to(torch.bfloat16)
+            o = torch.zeros(rows, nh * hd, dtype=torch.bfloat16, device=DEV)
+            nsplit = int(max(1, min(min(16, -(-T // 256)), -(-512 // (rows * nkv)))))
+            po, pl = torch.zeros(rows * nh * nsplit * hd, device=DEV), torch.zeros(rows * nh * nsplit, device=DEV)
+            cnt = torch.zeros(rows * nkv, dtype=torch.int32, device=DEV)
+            pos = torch.full((rows,), ctx - 1, dtype=torch.int32, device=DEV)
+            sl = [torch.arange(c * rows, (c + 1) * rows, dtype=torch.int32, device=DEV) for c in range(copies)]
+            fns = {"split": lambda i: kv8.attn_kv8(q, k8, v8, ks, vs, sl[i % copies], pos, rows, nh, nkv, hd, nsplit, po, pl, o,
+                                                   counters=cnt, min_chunk=256),
+                   "bf16_mfma": lambda i: hip._check(hip.lib().lsa_attn_decode_mfma(
+                       hip._p(q), q.stride(0), hip._p(kc), hip._p(vc), hip._p(sl[i % copies]), hip._p(pos), None, rows, nh, nkv,
+                       hd, T, hd ** -0.5, hip._p(o), o.stride(0), 0, hip._stream()), "lsa_attn_decode_mfma")}
+            for nw in (1, 2, 4):
+                fns[f"mfma_nw{nw}"] = lambda i, nw=nw: kv8.attn_kv8_mfma(q, k8, v8, ks, vs, sl[i % copies], pos, rows, nh, nkv,
+                                                                         hd, o, nw=nw)
+            r = _windows(fns, windows, reps=20)
+            line = {"kind": "gqa_attn", "heads": f"{nh}/{nkv}/{hd}", "rows": rows, "context": ctx, "nsplit": nsplit,
+                    "copies": copies, "bytes_kv8": b8, "bytes_bf16": b16, "windows": windows}
+            for k, (us, spread) in r.items():
+                line[k + "_us"], line[k + "_spread"] = round(us, 2), round(spread, 3)
+                line[k + "_TBps"] = round((b16 if k == "bf16_mfma" else b8) / us / 1e6, 3)
+            best = min(r[f"mfma_nw{nw}"][0] for nw in (1, 2, 4))
+            line["split_over_mfma_nw1"] = round(r["split"][0] / r["mfma_nw1"][0], 3)
+            line["bf16_mfma_over_best"] = round(r["bf16_mfma"][0] / best, 3)
+            print(json.dumps(line), flush=True)
+            out.append(line)
+            del k8, v8, kc, vc, ks, vs
+            torch.cuda.empty_cache()
+    cfg, ctx = get_preset("llama3.2-3b"), 143
+    e = _engine(cfg, "fp8", rows, -(-(ctx + n_steps + 2) // 64) * 64, rows)
+    for s in range(rows):
+        e.seq_len[s] = ctx - n_steps // 2
+    graphs, prev = {}, hip.ATTN_MFMA
+    try:
+        for name, on in (("mfma", True), ("split", False)):  # the route is taken when the graph is captured
+            hip.ATTN_MFMA = on
+            graphs[name] = DecodeGraph(e, rows, "full", slots=list(range(rows))).capture()
+    finally:
+        hip.ATTN_MFMA = prev
+
+    def run(g):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        g.set_positions()
+        g.replay()
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(n_steps):
+            g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n_steps
+    t = {k: [] for k in graphs}
+    for _ in range(windows):
+        for k in t:
+            t[k].append(run(graphs[k]))
+    line = {"kind": "gqa_step", "model": "llama3.2-3b", "batch": rows, "context": ctx, "steps_per_window": n_steps,
+            "windows": windows}
+    for k, v in t.items():
+        line[k + "_ms"] = round(statistics.median(v), 4)
+        line[k + "_spread"] = round((max(v) - min(v)) / statistics.median(v), 3)
+    line["ratio"] = round(line["split_ms"] / line["mfma_ms"], 3)
+    print(json.dumps(line), flush=True)
+    out.append(line)
+
+
 def bench(model: str, batch: int, n_steps: int, out: list) -> None:
     from llm_sharding_amd.parallel.pipeline import run_decode_benchmark
     for kvd in ("bf16", "fp8"):
@@ -207,7 +295,7 @@ def quality(model: str, out: list, n_seq: int = 4, prompt: int = 128, n_steps: i
 
 def main():
     ap = argparse.ArgumentParser()
-    for flag in ("--kernels", "--steps", "--bench", "--quality"):
+    for flag in ("--kernels", "--steps", "--bench", "--quality", "--gqa"):
         ap.add_argument(flag, action="store_true")
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--batches", default="512,1")
@@ -222,6 +310,8 @@ def main():
         kernels(a.windows, out)
     if a.steps:
         steps(a.model, [int(b) for b in a.batches.split(",")], a.windows, a.n_steps, a.context, out)
+    if a.gqa:
+        gqa(a.windows, a.n_steps, out)
     if a.bench:
         bench(a.model, 512, a.n_steps, out)
     if a.quality:
