@@ -84,7 +84,10 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     # per-file additions (the common flags stay as they are: they are part of every older object's
     # bits). kv8_mfma.hip: packed FP32 VALU switched off where the compiler knows the feature (one
     # that does not says so and ignores it; the ISA audit counts the packed instructions either way).
-    extra_flags = {"kv8_mfma.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+    # gemv_coop_int4.hip: the same, for the fp32 sums of its staging threads and of its split-K
+    # combine beside the MFMAs (its one vector add is also written element by element).
+    no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+    extra_flags = {"kv8_mfma.hip": no_pk, "gemv_coop_int4.hip": no_pk}
     jobs_list = []
     kobjs = []
     for s in kernel_srcs:

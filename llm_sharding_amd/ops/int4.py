@@ -1,5 +1,8 @@
 """Int4 weights (W4A16): the symmetric group-128 format, its packed layout for the gfx950 decode
-kernel (csrc/quant/gemv_int4.hip), the kernel's configs and its bindings.
+kernels, their configs and bindings, and the dispatcher between them (:func:`proj_int4`):
+csrc/quant/gemv_int4.hip for 1..64 rows (every workgroup reads all of A) and the cooperative
+csrc/quant/gemv_coop_int4.hip for 17..128 rows (a workgroup's waves share A through LDS, K split
+over workgroups), both on the same operands with the same arithmetic.
 
 The format is the ModelSharder's ``torch.int4`` one: ``w[n, k] ~= q[n, k] * scale[n, k // 128]``,
 ``|q| <= 7``, fp32 scales. On the device a projection is
@@ -143,6 +146,77 @@ def int4_config(n_tiles: int, rows: int, need_even: bool = False, k: int = 4096)
     return min(cands, key=cost)
 
 
+# (mb, tnw, nw, d) instantiated in csrc/quant/gemv_coop_int4.hip (LSA_INT4_COOP_CONFIGS) - keep in sync.
+# nw waves of tnw 16-column tiles each share a workgroup's A chunks; d = register-ring depth.
+INT4_COOP_CONFIGS = [(2, 1, 8, 4), (2, 1, 4, 4), (2, 2, 4, 4), (4, 1, 8, 4), (4, 1, 4, 4), (4, 2, 4, 3), (8, 1, 8, 3),
+                     (8, 1, 4, 3)]
+INT4_COOP_MIN_ROWS, INT4_COOP_MAX_ROWS = 17, 128  # rows the cooperative int4 kernel serves
+INT4_COOP_SPLITS = (1, 2, 4, 8, 16)
+INT4_COOP_SLAB_FLOATS = 1 << 24  # the smallest slab an engine's CoopWorkspace has (runtime/engine.py)
+
+
+def int4_coop_slab_floats(n: int, rows: int, tnw: int, nw: int, sk: int) -> int:
+    """fp32 workspace a cooperative int4 launch needs: sk partial tiles + partial sums of squares
+    (0 when sk == 1)."""
+    if sk <= 1:
+        return 0
+    mr = 16 * row_blocks(rows)
+    return sk * n * mr + sk * (n // 16 // (tnw * nw)) * mr
+
+
+def int4_coop_candidates(n_tiles: int, k: int, rows: int, need_even: bool = False) -> list:
+    """(tnw, nw, d, sk) for the cooperative int4 GEMV (17..128 rows): the workgroup's nw * tnw
+    tiles divide the tile count (need_even, SwiGLU: an even number of them), and every K split
+    keeps at least one 128-k group."""
+    if not INT4_COOP_MIN_ROWS <= rows <= INT4_COOP_MAX_ROWS or k % INT4_GROUP or k < INT4_GROUP:
+        return []
+    mb = row_blocks(rows)
+    out = []
+    for (b, tnw, nw, d) in INT4_COOP_CONFIGS:
+        tg = tnw * nw
+        if b != mb or n_tiles % tg or (need_even and tg % 2):
+            continue
+        out += [(tnw, nw, d, sk) for sk in INT4_COOP_SPLITS
+                if sk <= k // INT4_GROUP and (n_tiles // tg) * sk <= 4 * N_CU]
+    return out
+
+
+INT4_COOP_MIN_GRID = 160   # workgroups from which a wider grid measured no faster than a lesser K split
+INT4_COOP_MIN_CHUNKS = 8   # 128-k groups a K split keeps (shorter pipelines lost to their own ramp and epilogue)
+
+
+def int4_coop_config(n_tiles: int, k: int, rows: int, need_even: bool = False,
+                     slab_floats: int = INT4_COOP_SLAB_FLOATS, counters: Optional[int] = None) -> Optional[tuple]:
+    """(tnw, nw, d, sk) or None when no built config divides the tile count (or fits a workspace
+    of ``slab_floats`` floats and, if given, ``counters`` arrival counters). The rule that reproduces the winners of profiles/int4.md "Cooperative
+    kernel": a grid of at least INT4_COOP_MIN_GRID workgroups whose K splits keep
+    INT4_COOP_MIN_CHUNKS groups each (every split writes and re-reads an fp32 tile of all rows
+    and pays the pipeline's ramp); among those the widest workgroup (A is staged once per column
+    group), one tile per wave, the fewest splits. Where no config reaches that: the largest grid
+    up to one workgroup per CU, then the fewest splits."""
+    cands = [c for c in int4_coop_candidates(n_tiles, k, rows, need_even)
+             if int4_coop_slab_floats(16 * n_tiles, rows, c[0], c[1], c[3]) <= slab_floats
+             and (counters is None or n_tiles // (c[0] * c[1]) <= counters)]
+    if not cands:
+        return None
+
+    def cost(c):
+        tnw, nw, d, sk = c
+        grid = n_tiles // (tnw * nw) * sk
+        ok = grid >= INT4_COOP_MIN_GRID and (sk == 1 or k // INT4_GROUP // sk >= INT4_COOP_MIN_CHUNKS)
+        return (not ok, 0 if ok else -min(grid, N_CU), -tnw * nw, -nw, sk)
+    return min(cands, key=cost)
+
+
+# Rows 17..64: the (N, K, row blocks) classes where the cooperative kernel measured faster than
+# gemv_int4 by more than the two windows' spread, each with the table that measured it (2 row
+# blocks: at 32 rows, 4: at 64 rows). Rows 65..128 always take the cooperative kernel: the
+# alternative there is dequantise + bf16, which it beat on every measured shape.
+_COOP_TABLE = 'profiles/int4.md "Cooperative kernel, Llama-2-7B shapes"'
+INT4_COOP_ROUTE = {(n, k, mb): _COOP_TABLE
+                   for n, k in ((12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)) for mb in (2, 4)}
+
+
 # ------------------------------------------------------------------------------ bindings
 _L = None
 
@@ -158,6 +232,10 @@ def _lib():
         L.lsa_gemv_int4.argtypes = [vp, i, vp, vp, vp, i, i, i, i, f, i, ctypes.POINTER(hip.EpiArgs), i, i, i, vp]
         L.lsa_dequant_int4_packed.argtypes = [vp, vp, vp, i, i, vp]
         L.lsa_gemv_int4.restype = L.lsa_dequant_int4_packed.restype = i
+        if not hasattr(L, "lsa_gemv_coop_int4"):
+            raise RuntimeError("the kernel library has no lsa_gemv_coop_int4: rebuild it (python csrc/build.py)")
+        L.lsa_gemv_coop_int4.argtypes = [vp, i, vp, vp, vp, i, i, i, i, f, i, ctypes.POINTER(hip.EpiArgs), i, i, i, i, vp, vp, vp]
+        L.lsa_gemv_coop_int4.restype = i
         _L = L
     return _L
 
@@ -188,6 +266,64 @@ def gemv_int4(x: torch.Tensor, wq4: torch.Tensor, scales: torch.Tensor, M: int, 
     rc = _lib().lsa_gemv_int4(hip._p(x), x.stride(0), hip._p(a_rows), hip._p(wq4), hip._p(scales), M, N, K, int(norm), float(eps), epi,
                              ctypes.byref(ep), tn, nw, ug, hip._stream())
     hip._check(rc, "lsa_gemv_int4")
+
+
+def gemv_coop_int4(x: torch.Tensor, wq4: torch.Tensor, scales: torch.Tensor, M: int, N: int, K: int, epi: int,
+                   ep: hip.EpiArgs, norm: bool = False, eps: float = 1e-5, ws: Optional[hip.CoopWorkspace] = None,
+                   a_rows: Optional[torch.Tensor] = None, cfg: Optional[tuple] = None) -> None:
+    """Cooperative W4A16 decode projection (csrc/quant/gemv_coop_int4.hip), 17 <= M <= 128, on
+    :func:`gemv_int4`'s operands. ``cfg`` = (tnw, nw, d, sk), default :func:`int4_coop_config`;
+    ``ws``: the split-K slab and arrival counters (default: the process-wide workspace)."""
+    hip._req(INT4_COOP_MIN_ROWS <= M <= INT4_COOP_MAX_ROWS, f"gemv_coop_int4 supports 17..128 rows, got {M}")
+    hip._req(epi in (hip.EPI_STORE, hip.EPI_RESID, hip.EPI_SWIGLU, hip.EPI_QKV), f"gemv_coop_int4: epilogue {epi} not built")
+    hip._check_epi(epi, ep, N)
+    hip._req(hip._is_bf16_cuda(x), "gemv_coop_int4: bf16 cuda activations")
+    hip._req(N >= 16 and N % 16 == 0 and K >= 128 and K % 128 == 0, "gemv_coop_int4: N % 16, K % 128")
+    hip._req(wq4.is_cuda and wq4.dtype == torch.uint8 and wq4.numel() == N * K // 2,
+             "gemv_coop_int4: packed int4 weights [N*K/2] uint8")
+    hip._req(scales.is_cuda and scales.dtype == torch.float32 and scales.numel() == N * (K // 128)
+             and scales.is_contiguous(), "gemv_coop_int4: packed fp32 group scales [N*K/128]")
+    hip._req(x.dim() == 2 and x.shape[1] >= K and x.stride(1) == 1, "gemv_coop_int4: x must be [rows, >=K] row-major")
+    if a_rows is None:
+        hip._req(x.shape[0] >= M, "gemv_coop_int4: x has fewer rows than M")
+    else:
+        hip._req(a_rows.dtype == torch.int32 and a_rows.is_cuda and a_rows.numel() >= M, "gemv_coop_int4: a_rows")
+    if ws is None:
+        ws = hip.default_workspace(x.device)
+    if cfg is None:
+        cfg = int4_coop_config(N // 16, K, M, epi == hip.EPI_SWIGLU, ws.slab.numel())
+        hip._req(cfg is not None, f"gemv_coop_int4: no config for N={N} K={K} M={M}")
+    cfg = tuple(cfg)
+    hip._req(cfg in int4_coop_candidates(N // 16, K, M, epi == hip.EPI_SWIGLU),
+             f"gemv_coop_int4: config {cfg} not built or invalid for N={N} K={K} M={M}")
+    tnw, nw, d, sk = cfg
+    need = int4_coop_slab_floats(N, M, tnw, nw, sk)
+    hip._req(ws.slab.numel() >= need, f"gemv_coop_int4: workspace too small ({ws.slab.numel()} < {need} floats)")
+    hip._req(ws.counters.numel() >= N // 16 // (tnw * nw), "gemv_coop_int4: workspace counters too small")
+    rc = _lib().lsa_gemv_coop_int4(hip._p(x), x.stride(0), hip._p(a_rows), hip._p(wq4), hip._p(scales), M, N, K, int(norm),
+                                  float(eps), epi, ctypes.byref(ep), tnw, nw, d, sk, hip._p(ws.slab), hip._p(ws.counters),
+                                  hip._stream())
+    hip._check(rc, "lsa_gemv_coop_int4")
+
+
+def proj_int4(x: torch.Tensor, wq4: torch.Tensor, scales: torch.Tensor, M: int, N: int, K: int, epi: int,
+              ep: hip.EpiArgs, norm: bool = False, eps: float = 1e-5, ws: Optional[hip.CoopWorkspace] = None,
+              a_rows: Optional[torch.Tensor] = None) -> bool:
+    """The int4 decode projection of ``M`` rows on its native kernel: :func:`gemv_int4` up to 64
+    rows, :func:`gemv_coop_int4` from 65 to 128 and, from 17 to 64, for the classes of
+    ``INT4_COOP_ROUTE``. False (nothing launched) where no native kernel serves the shape: the
+    caller dequantises and runs the bf16 kernels."""
+    coop = None
+    if INT4_COOP_MIN_ROWS <= M <= INT4_COOP_MAX_ROWS and (M > INT4_MAX_ROWS or (N, K, row_blocks(M)) in INT4_COOP_ROUTE):
+        w = ws if ws is not None else hip.default_workspace(x.device)
+        coop = int4_coop_config(N // 16, K, M, epi == hip.EPI_SWIGLU, w.slab.numel(), w.counters.numel())
+    if coop is not None:
+        gemv_coop_int4(x, wq4, scales, M, N, K, epi, ep, norm=norm, eps=eps, ws=ws, a_rows=a_rows, cfg=coop)
+    elif M <= INT4_MAX_ROWS:
+        gemv_int4(x, wq4, scales, M, N, K, epi, ep, norm=norm, eps=eps, a_rows=a_rows)
+    else:
+        return False
+    return True
 
 
 def dequant_int4_packed(wq4: torch.Tensor, scales: torch.Tensor, out: torch.Tensor, N: int, K: int) -> torch.Tensor:

@@ -3,10 +3,12 @@
 ``make_stage_engine(..., weight_dtype="int4")`` (what ``inference.py --weight-dtype int4`` and
 ``PipelineStage(weight_dtype="int4")`` build) keeps the four projections of every layer as
 symmetric group-128 int4 with fp32 group scales - 4.25 bits per weight (ops/int4.py). Decode
-batches of up to 64 rows stream them through csrc/quant/gemv_int4.hip; larger row counts
-dequantise one projection at a time into ``w_scratch`` and run the bf16 kernels (the cooperative
-GEMV up to ``GEMV_MAX_ROWS`` rows, the GEMMs above and for prefill, with the same fused-norm and
-split-K-partial routes), as the fp8 engine does.
+batches of up to 128 rows stream them through the int4 kernels, chosen by ``int4.proj_int4``:
+csrc/quant/gemv_int4.hip up to 64 rows, the cooperative csrc/quant/gemv_coop_int4.hip from 65 to
+128 rows (and below where ``int4.INT4_COOP_ROUTE`` lists the shape). Larger row counts, prefill and
+a shape no cooperative config divides dequantise one projection at a time into ``w_scratch`` and
+run the bf16 kernels (the cooperative GEMV up to ``GEMV_MAX_ROWS`` rows, the GEMMs above and for
+prefill, with the same fused-norm and split-K-partial routes), as the fp8 engine does.
 
 The lm_head, the embedding and the norms stay bf16 (``lm_head_s`` stays None), so ``head``,
 ``Sampler``, the logit stages and ``score_prompt`` are the bf16 engine's, unchanged. Each fused
@@ -59,14 +61,14 @@ class Int4StageEngine(StageEngine):
 
     def _alloc_runtime(self) -> None:
         super()._alloc_runtime()
-        if self.int4:  # one projection's bf16 weights, for the > 64-row paths
+        if self.int4:  # one projection's bf16 weights, for the > 128-row and prefill paths
             shapes = self.proj_shapes(self.cfg)
             self.w_scratch = torch.empty(max(n * k for n, k in shapes), dtype=torch.bfloat16, device=self.device)
 
     # ------------------------------------------------------------------------- HIP path
     # _forward_hip / _forward_hip_gpt2 are StageEngine's, statement for statement, with the three
-    # weight closures (wbf, dec, pre; GPT-2: proj) dispatching on the int4 weights: native kernel up
-    # to 64 rows, else dequantise into w_scratch and the SAME bf16 route the base engine takes for
+    # weight closures (wbf, dec, pre; GPT-2: proj) dispatching on the int4 weights: the native kernels
+    # up to 128 decode rows (int4.proj_int4), else dequantise into w_scratch and the SAME bf16 route the base engine takes for
     # that row count (cooperative GEMV, gemm_sk with the fused RMSNorm sums and the split-K
     # partial residuals, gemm_wr), as its fp8 weights do. tests/test_int4.py pins that the two
     # bodies differ in those closures only, so a change of the base forward fails until it is
@@ -90,14 +92,14 @@ class Int4StageEngine(StageEngine):
         q, attn_o, act, xn = self.buf_q[:rows], self.buf_attn[:rows], self.buf_act[:rows], self.buf_xn[:rows]
         ws = self.coop_ws
         native_fp8 = False  # int4 weights: the name stays so that the rest of the body is the base engine's
-        native_int4 = rows <= int4.INT4_MAX_ROWS
+        native_int4 = rows <= int4.INT4_COOP_MAX_ROWS
         if cfg.is_gpt2:
             return self._forward_hip_gpt2(hbuf, slot, pos, kv_len, rows, nsplit, tiles, decode, native_int4)
         wbf = self._weights_bf16  # packed bf16 weights (int4 -> scratch for the larger-row kernels)
 
         def dec(x, w, s, N, K, epi, ep, norm=False):
-            if native_int4:
-                int4.gemv_int4(x, w, s, rows, N, K, epi, ep, norm=norm, eps=eps)
+            if native_int4 and int4.proj_int4(x, w, s, rows, N, K, epi, ep, norm=norm, eps=eps, ws=ws):
+                pass  # launched on an int4 kernel; False: no config for the shape, dequantise
             else:
                 hip.gemv(x, wbf(w, s, N, K), rows, N, K, epi, ep, norm=norm, eps=eps, ws=ws)
 
@@ -223,8 +225,7 @@ class Int4StageEngine(StageEngine):
         ws = self.coop_ws
 
         def proj(x, w, s, N, K, epi, ep):
-            if decode and native_int4:
-                int4.gemv_int4(x, w, s, rows, N, K, epi, ep)
+            if decode and native_int4 and int4.proj_int4(x, w, s, rows, N, K, epi, ep, ws=ws):
                 return
             wb = self._weights_bf16(w, s, N, K)
             if decode:

@@ -6,7 +6,9 @@
   kernel; every candidate is timed once, then the winners in alternating windows over weight
   copies that exceed the Infinity Cache (cold stream). Reports the median and the spread
   (max - min) / median of the windows.
---steps: ms per token of a random-init model (default llama2-7b) at batch 1 and 16, one captured
+--coop: the cooperative int4 kernel (17..128 rows) at 32, 64, 96 and 128 rows against the plain int4
+  kernel (up to 64 rows), the best cooperative fp8 config and dequantise + bf16, by the same method.
+--steps: ms per token of a random-init model (default llama2-7b) at batch 1, 16, 64 and 128, one captured
   decode graph per weight dtype, the dtypes alternated window by window in one process.
 One JSON line per result; everything is also written to --out."""
 import argparse
@@ -34,7 +36,7 @@ def _windows(fns: dict, windows: int) -> dict:
     return {k: (statistics.median(v), (max(v) - min(v)) / statistics.median(v)) for k, v in t.items()}
 
 
-def kernels(model: str, rows_list, windows: int, out: list) -> None:
+def kernels(model: str, rows_list, windows: int, out: list, coop: bool = False) -> None:
     from llm_sharding_amd.config import llama2_7b
     from llm_sharding_amd.models.rope import rope_table
     cos, sin = rope_table(llama2_7b(), 1024, DEV)
@@ -78,6 +80,11 @@ def kernels(model: str, rows_list, windows: int, out: list) -> None:
                 hip.gemv(x, int4.dequant_int4_packed(w4[i % nb], sc4[i % nb], scratch, N, K), M, N, K, epi, ep, norm=norm,
                          ws=cws)
 
+            if coop:
+                _coop_row(name, N, K, M, even, f4, f8, fdq, cws, windows, out,
+                          lambda cfg: lambda i: int4.gemv_coop_int4(x, w4[i % nb], sc4[i % nb], M, N, K, epi, ep, norm=norm,
+                                                                    ws=cws, cfg=cfg))
+                continue
             c4 = sorted((timeit(f4(c)), c) for c in int4.int4_gemv_candidates(N // 16, K, M, even))
             a8 = [("fp8", c) for c in packing.fp8_gemv_candidates(N // 16, K, M, even)] + \
                  [("coop_fp8", c) for c in packing.coop_fp8_candidates(N // 16, K, M)]
@@ -104,6 +111,30 @@ def kernels(model: str, rows_list, windows: int, out: list) -> None:
             out.append(line)
         del w4, sc4, w8, scratch
         torch.cuda.empty_cache()
+
+
+def _coop_row(name, N, K, M, even, f4, f8, fdq, cws, windows, out, fc) -> None:
+    """One row of the cooperative table: the best coop_int4 config (and the rule's, where it is
+    another) against the plain int4 kernel (up to 64 rows), the best cooperative fp8 config and
+    dequantise + the bf16 kernel, the engine's route above 64 rows without the cooperative kernel."""
+    cc = sorted((timeit(fc(c)), c) for c in int4.int4_coop_candidates(N // 16, K, M, even)
+                if int4.int4_coop_slab_floats(N, M, c[0], c[1], c[3]) <= cws.slab.numel())
+    c8 = sorted((timeit(f8(("coop_fp8", c))), c) for c in packing.coop_fp8_candidates(N // 16, K, M))
+    auto = int4.int4_coop_config(N // 16, K, M, even)
+    fns = {"coop_int4": fc(cc[0][1]), "fp8": f8(("coop_fp8", c8[0][1])), "dequant+bf16": fdq}
+    if auto != cc[0][1]:
+        fns["coop_int4_auto"] = fc(auto)
+    if M <= int4.INT4_MAX_ROWS:
+        fns["int4"] = f4(int4.int4_config(N // 16, M, even, K))
+    r = _windows(fns, windows)
+    line = {"table": "coop", "shape": name, "N": N, "K": K, "M": M, "coop_int4_cfg": list(cc[0][1]),
+            "coop_int4_auto_cfg": list(auto), "fp8_cfg": list(c8[0][1]),
+            "coop_int4_TBps": round(int4.int4_bytes(N, K) / r["coop_int4"][0] / 1e6, 2),
+            "coop_int4_sweep": [(round(t, 2),) + tuple(c) for t, c in cc]}
+    for k, (us, spread) in r.items():
+        line[k + "_us"], line[k + "_spread"] = round(us, 2), round(spread, 3)
+    print(json.dumps(line), flush=True)
+    out.append(line)
 
 
 def steps(model: str, batches, windows: int, n_steps: int, out: list) -> None:
@@ -150,10 +181,12 @@ def steps(model: str, batches, windows: int, n_steps: int, out: list) -> None:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--coop", action="store_true", help="the cooperative int4 kernel's table (rows 17..128)")
     ap.add_argument("--steps", action="store_true")
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--rows", default="1,16,64")
-    ap.add_argument("--batches", default="1,16")
+    ap.add_argument("--coop-rows", default="32,64,96,128")
+    ap.add_argument("--batches", default="1,16,64,128")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--n-steps", type=int, default=64)
     ap.add_argument("--out", default="bench_int4.json")
@@ -162,6 +195,8 @@ def main():
     out = []
     if a.kernels:
         kernels(a.model, [int(r) for r in a.rows.split(",")], a.windows, out)
+    if a.coop:
+        kernels(a.model, [int(r) for r in a.coop_rows.split(",")], a.windows, out, coop=True)
     if a.steps:
         steps(a.model, [int(b) for b in a.batches.split(",")], a.windows, a.n_steps, out)
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
