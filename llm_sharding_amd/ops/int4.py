@@ -2,7 +2,8 @@
 kernels, their configs and bindings, and the dispatcher between them (:func:`proj_int4`):
 csrc/quant/gemv_int4.hip for 1..64 rows (every workgroup reads all of A) and the cooperative
 csrc/quant/gemv_coop_int4.hip for 17..128 rows (a workgroup's waves share A through LDS, K split
-over workgroups), both on the same operands with the same arithmetic.
+over workgroups), and csrc/quant/gemm_int4.hip for prefill chunks and decode batches above 128 rows
+(:func:`proj_gemm_int4`), all on the same operands with the same arithmetic.
 
 The format is the ModelSharder's ``torch.int4`` one: ``w[n, k] ~= q[n, k] * scale[n, k // 128]``,
 ``|q| <= 7``, fp32 scales. On the device a projection is
@@ -19,6 +20,7 @@ engine and csrc/kernels/ are the recorded inputs of the bf16 decode path's full-
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional
 
 import torch
@@ -217,6 +219,61 @@ INT4_COOP_ROUTE = {(n, k, mb): _COOP_TABLE
                    for n, k in ((12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008)) for mb in (2, 4)}
 
 
+# (bn, depth) instantiated in csrc/quant/gemm_int4.hip (lsa_gemm_int4) - keep in sync. 128-row x bn
+# tiles, depth = groups in the A ring. bn 256 is not built: its accumulators, group partials and
+# rings spilled (the kernel's header comment has the compiler's report).
+INT4_GEMM_CONFIGS = [(128, 4)]
+INT4_GEMM_SPLITS = (1, 2, 4, 8)
+INT4_GEMM_ROWS = 128          # rows of an output tile
+INT4_GEMM_MIN_GRID = 192      # workgroups from which a further K split measured no faster
+INT4_GEMM_MIN_CHUNKS = 4      # 128-k groups a K split keeps: the depth of the A ring
+# output tiles (ceil(M/128) * N/bn) up to which the native GEMM measured ahead of dequantise + bf16
+# GEMM by more than the windows' spread: the o and down projections at 256 rows (64 tiles); from 128
+# tiles on it was level or behind on every shape (profiles/int4.md "GEMM, Llama-2-7B shapes")
+INT4_GEMM_MAX_TILES = 64
+
+
+def _row_tiles(M: int) -> int:
+    return -(-M // INT4_GEMM_ROWS)
+
+
+def int4_gemm_slab_floats(M: int, N: int, sk: int) -> int:
+    """fp32 workspace a split int4 GEMM launch needs: sk partial tiles of whole 128-row tiles
+    (0 when sk == 1)."""
+    return 0 if sk <= 1 else sk * _row_tiles(M) * INT4_GEMM_ROWS * N
+
+
+def int4_gemm_candidates(M: int, N: int, K: int, epi: int = 0) -> list:
+    """(bn, sk) the int4 GEMM can run: bn divides N, every K split keeps a 128-k group, the
+    partial slab stays under 2 GiB."""
+    if M < 1 or N < 1 or K < INT4_GROUP or K % INT4_GROUP or epi not in (hip.EPI_STORE, hip.EPI_RESID, hip.EPI_SWIGLU, hip.EPI_QKV):
+        return []
+    return [(bn, sk) for bn, _ in INT4_GEMM_CONFIGS if N % bn == 0 for sk in INT4_GEMM_SPLITS
+            if sk <= K // INT4_GROUP and 4 * int4_gemm_slab_floats(M, N, sk) < 1 << 31]
+
+
+def int4_gemm_config(M: int, N: int, K: int, epi: int = 0, slab_floats: int = INT4_COOP_SLAB_FLOATS,
+                     counters: Optional[int] = None) -> Optional[tuple]:
+    """(bn, sk) or None when no built tile divides N (or nothing fits a workspace of
+    ``slab_floats`` floats and, if given, ``counters`` arrival counters). The rule that reproduces
+    the winners of profiles/int4.md "GEMM, Llama-2-7B shapes": the fewest K splits that give at
+    least INT4_GEMM_MIN_GRID workgroups (ceil(M/128) * N/bn tiles x sk) while every split keeps
+    INT4_GEMM_MIN_CHUNKS groups (each split writes and the last arriver re-reads an fp32 tile, and
+    pays the ring's ramp); where no split reaches that grid, the most splits that keep the chunks."""
+    cands = [(bn, sk) for bn, sk in int4_gemm_candidates(M, N, K, epi)
+             if int4_gemm_slab_floats(M, N, sk) <= slab_floats
+             and (counters is None or sk == 1 or _row_tiles(M) * (N // bn) <= counters)]
+    if not cands:
+        return None
+
+    def cost(c):
+        bn, sk = c
+        grid = _row_tiles(M) * (N // bn) * sk
+        deep = sk == 1 or K // INT4_GROUP // sk >= INT4_GEMM_MIN_CHUNKS
+        return (not deep, grid < INT4_GEMM_MIN_GRID, sk if grid >= INT4_GEMM_MIN_GRID else -sk)
+    return min(cands, key=cost)
+
+
 # ------------------------------------------------------------------------------ bindings
 _L = None
 
@@ -236,6 +293,10 @@ def _lib():
             raise RuntimeError("the kernel library has no lsa_gemv_coop_int4: rebuild it (python csrc/build.py)")
         L.lsa_gemv_coop_int4.argtypes = [vp, i, vp, vp, vp, i, i, i, i, f, i, ctypes.POINTER(hip.EpiArgs), i, i, i, i, vp, vp, vp]
         L.lsa_gemv_coop_int4.restype = i
+        if not hasattr(L, "lsa_gemm_int4"):
+            raise RuntimeError("the kernel library has no lsa_gemm_int4: rebuild it (python csrc/build.py)")
+        L.lsa_gemm_int4.argtypes = [vp, i, vp, vp, i, i, i, i, ctypes.POINTER(hip.EpiArgs), i, i, i, vp, ctypes.c_longlong, vp, i, vp]
+        L.lsa_gemm_int4.restype = i
         _L = L
     return _L
 
@@ -324,6 +385,77 @@ def proj_int4(x: torch.Tensor, wq4: torch.Tensor, scales: torch.Tensor, M: int, 
     else:
         return False
     return True
+
+
+def gemm_int4(x: torch.Tensor, wq4: torch.Tensor, scales: torch.Tensor, M: int, N: int, K: int, epi: int,
+              ep: hip.EpiArgs, ws: Optional[hip.CoopWorkspace] = None, cfg: Optional[tuple] = None) -> None:
+    """W4A16 GEMM (csrc/quant/gemm_int4.hip), any M >= 1, on :func:`gemv_int4`'s operands; the
+    rows of ``x`` 16-byte aligned. ``cfg`` = (bn, sk), default :func:`int4_gemm_config`; ``ws``: the
+    split-K slab and arrival counters (default: the process-wide workspace). The fused-RMSNorm
+    fields of ``ep`` as in ``hip.gemm_sk``: ``ss_in`` (QKV / SWIGLU, K == 64 ss_n), ``ss_out`` (RESID)."""
+    hip._req(M >= 1, f"gemm_int4 needs at least one row, got {M}")
+    hip._req(epi in (hip.EPI_STORE, hip.EPI_RESID, hip.EPI_SWIGLU, hip.EPI_QKV), f"gemm_int4: epilogue {epi} not built")
+    hip._check_epi(epi, ep, N)
+    hip._req(hip._is_bf16_cuda(x), "gemm_int4: bf16 cuda activations")
+    hip._req(N >= 16 and N % 16 == 0 and K >= 128 and K % 128 == 0, "gemm_int4: N % 16, K % 128")
+    hip._req(wq4.is_cuda and wq4.dtype == torch.uint8 and wq4.numel() == N * K // 2,
+             "gemm_int4: packed int4 weights [N*K/2] uint8")
+    hip._req(scales.is_cuda and scales.dtype == torch.float32 and scales.numel() == N * (K // 128)
+             and scales.is_contiguous(), "gemm_int4: packed fp32 group scales [N*K/128]")
+    hip._req(x.dim() == 2 and x.shape[1] >= K and x.stride(1) == 1 and x.shape[0] >= M,
+             "gemm_int4: x must be [>=M, >=K] row-major")
+    hip._req(x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and M * x.stride(0) < 1 << 30,
+             "gemm_int4: rows of x must be 16-byte aligned")
+    hip._req(not ep.ss_in or (epi in (hip.EPI_QKV, hip.EPI_SWIGLU) and K == 64 * ep.ss_n and ep.ss_n % 4 == 0),
+             "gemm_int4: ss_in needs a QKV / SWIGLU epilogue and K == 64 ss_n")
+    hip._req(not ep.ss_out or (epi == hip.EPI_RESID and N == 64 * ep.ss_n), "gemm_int4: ss_out needs a RESID epilogue and N == 64 ss_n")
+    hip._req(epi != hip.EPI_SWIGLU or not ep.bias, "gemm_int4: no bias on the SwiGLU epilogue")
+    if ws is None:
+        ws = hip.default_workspace(x.device)
+    if cfg is None:
+        cfg = int4_gemm_config(M, N, K, epi, ws.slab.numel(), ws.counters.numel())
+        hip._req(cfg is not None, f"gemm_int4: no config for N={N} K={K} M={M}")
+    cfg = tuple(cfg)
+    hip._req(cfg in int4_gemm_candidates(M, N, K, epi), f"gemm_int4: config {cfg} not built or invalid for N={N} K={K} M={M}")
+    bn, sk = cfg
+    depth = dict(INT4_GEMM_CONFIGS)[bn]
+    need = int4_gemm_slab_floats(M, N, sk)
+    hip._req(ws.slab.numel() >= need, f"gemm_int4: workspace too small ({ws.slab.numel()} < {need} floats)")
+    hip._req(sk == 1 or ws.counters.numel() >= _row_tiles(M) * (N // bn), "gemm_int4: workspace counters too small")
+    rc = _lib().lsa_gemm_int4(hip._p(x), x.stride(0), hip._p(wq4), hip._p(scales), M, N, K, epi, ctypes.byref(ep), bn, depth, sk,
+                             hip._p(ws.slab), ws.slab.numel(), hip._p(ws.counters), ws.counters.numel(), hip._stream())
+    hip._check(rc, "lsa_gemm_int4")
+
+
+def int4_gemm_enabled() -> bool:
+    """The run-time switch, read at every call: ``LSA_INT4_GEMM=1`` routes to the native GEMM. Off
+    by default: above 128 rows an int4 engine is pinned to the bits of the bf16 kernels on the
+    dequantised (bf16-rounded) weights (tests/test_engine_edges_gpu.py), which a kernel that never
+    rounds the weights cannot give, and the kernel is ahead on small tile counts only."""
+    return os.environ.get("LSA_INT4_GEMM", "0") == "1"
+
+
+def proj_gemm_int4(x: torch.Tensor, wq4: torch.Tensor, scales: Optional[torch.Tensor], M: int, N: int, K: int, epi: int,
+                   ep: hip.EpiArgs, ws: Optional[hip.CoopWorkspace] = None) -> bool:
+    """A prefill chunk or a decode batch above 128 rows on the native int4 GEMM, for shapes of up
+    to ``INT4_GEMM_MAX_TILES`` output tiles. False (nothing launched) where the weights are not
+    int4, the switch is off, no config serves the shape or it has more tiles (there the bf16 GEMM
+    on dequantised weights measured level or faster): the caller dequantises."""
+    if scales is None or not int4_gemm_enabled():
+        return False
+    w = ws if ws is not None else hip.default_workspace(x.device)
+    cfg = int4_gemm_config(M, N, K, epi, w.slab.numel(), w.counters.numel())
+    if cfg is None or _row_tiles(M) * (N // cfg[0]) > INT4_GEMM_MAX_TILES:
+        return False
+    gemm_int4(x, wq4, scales, M, N, K, epi, ep, ws=w, cfg=cfg)
+    return True
+
+
+def int4_gemm_serves(shapes, rows: int, slab_floats: int = INT4_COOP_SLAB_FLOATS, counters: Optional[int] = None) -> bool:
+    """Whether :func:`proj_gemm_int4` takes every (N, K) of ``shapes`` at ``rows`` rows."""
+    cfgs = [int4_gemm_config(rows, n, k, hip.EPI_STORE, slab_floats, counters) for n, k in shapes]
+    return int4_gemm_enabled() and all(c is not None and _row_tiles(rows) * (n // c[0]) <= INT4_GEMM_MAX_TILES
+                                       for c, (n, _) in zip(cfgs, shapes))
 
 
 def dequant_int4_packed(wq4: torch.Tensor, scales: torch.Tensor, out: torch.Tensor, N: int, K: int) -> torch.Tensor:

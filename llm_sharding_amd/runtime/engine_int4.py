@@ -5,9 +5,12 @@
 symmetric group-128 int4 with fp32 group scales - 4.25 bits per weight (ops/int4.py). Decode
 batches of up to 128 rows stream them through the int4 kernels, chosen by ``int4.proj_int4``:
 csrc/quant/gemv_int4.hip up to 64 rows, the cooperative csrc/quant/gemv_coop_int4.hip from 65 to
-128 rows (and below where ``int4.INT4_COOP_ROUTE`` lists the shape). Larger row counts, prefill and
-a shape no cooperative config divides dequantise one projection at a time into ``w_scratch`` and
-run the bf16 kernels (the cooperative GEMV up to ``GEMV_MAX_ROWS`` rows, the GEMMs above and for
+128 rows (and below where ``int4.INT4_COOP_ROUTE`` lists the shape). With ``LSA_INT4_GEMM=1`` larger decode batches and
+prefill chunks run the W4A16 GEMM csrc/quant/gemm_int4.hip where it measured ahead: shapes of up to
+``int4.INT4_GEMM_MAX_TILES`` 128 x 128 output tiles (``int4.proj_gemm_int4``: the fused-RMSNorm
+fields included, the residual projections on its EPI_RESID epilogue when all four projections
+qualify). Larger shapes, a shape no native config divides and the default (``LSA_INT4_GEMM`` unset: the
+bits of the bf16 kernels on the bf16-rounded weights, which tests/test_engine_edges_gpu.py pins) dequantise one projection at a time into ``w_scratch`` and run the bf16 kernels (the cooperative GEMV up to ``GEMV_MAX_ROWS`` rows, the GEMMs above and for
 prefill, with the same fused-norm and split-K-partial routes), as the fp8 engine does.
 
 The lm_head, the embedding and the norms stay bf16 (``lm_head_s`` stays None), so ``head``,
@@ -65,10 +68,19 @@ class Int4StageEngine(StageEngine):
             shapes = self.proj_shapes(self.cfg)
             self.w_scratch = torch.empty(max(n * k for n, k in shapes), dtype=torch.bfloat16, device=self.device)
 
+    def _alloc_part_k(self, R: int):
+        """No split-K partial buffer where the native int4 GEMM takes all four projections at every
+        row count up to ``R``: the residual projections then run its EPI_RESID (+ ss_out) epilogue."""
+        ws = self.coop_ws
+        if self.int4 and all(int4.int4_gemm_serves(self.proj_shapes(self.cfg), m, ws.slab.numel(), ws.counters.numel())
+                             for m in range(int4.INT4_GEMM_ROWS, R + 1, int4.INT4_GEMM_ROWS)):
+            return None
+        return super()._alloc_part_k(R)
+
     # ------------------------------------------------------------------------- HIP path
     # _forward_hip / _forward_hip_gpt2 are StageEngine's, statement for statement, with the three
     # weight closures (wbf, dec, pre; GPT-2: proj) dispatching on the int4 weights: the native kernels
-    # up to 128 decode rows (int4.proj_int4), else dequantise into w_scratch and the SAME bf16 route the base engine takes for
+    # (int4.proj_int4 up to 128 decode rows, int4.proj_gemm_int4 above and for prefill), else dequantise into w_scratch and the SAME bf16 route the base engine takes for
     # that row count (cooperative GEMV, gemm_sk with the fused RMSNorm sums and the split-K
     # partial residuals, gemm_wr), as its fp8 weights do. tests/test_int4.py pins that the two
     # bodies differ in those closures only, so a change of the base forward fails until it is
@@ -117,6 +129,7 @@ class Int4StageEngine(StageEngine):
             hip.resid_rmsnorm_partials(hbuf, part, pc[3], rows, eps)
 
         def pre(x, w, s, N, K, epi, ep):
+            if int4.proj_gemm_int4(x, w, s, rows, N, K, epi, ep, ws=ws): return  # else dequantise
             hip.gemm(x, wbf(w, s, N, K), rows, N, K, epi, ep, ws=ws, sk_ws=self.sk_ws)
 
         # residual projections as split-K partials summed by the next norm kernel, where measured
@@ -125,6 +138,7 @@ class Int4StageEngine(StageEngine):
         # LDS-DMA MFMA GEMMs (gemm_sk / gemm_wr) above - independent of the attention's decode mode
         proj_gemm = (not decode) or (rows > self.GEMV_MAX_ROWS and not native_fp8 and self.sk_ws is not None)
         part_ok = proj_gemm and self.part_k is not None and rows <= self.part_k.shape[1]
+        part_ok = part_ok and not int4.int4_gemm_serves(self.proj_shapes(cfg), rows, ws.slab.numel(), ws.counters.numel())
 
         def resid_proj(x, w, s, N, K, ep):
             # returns the split count of partials left in part_k (0: residual applied in-GEMM)
@@ -227,6 +241,7 @@ class Int4StageEngine(StageEngine):
         def proj(x, w, s, N, K, epi, ep):
             if decode and native_int4 and int4.proj_int4(x, w, s, rows, N, K, epi, ep, ws=ws):
                 return
+            if not decode and int4.proj_gemm_int4(x, w, s, rows, N, K, epi, ep, ws=ws): return
             wb = self._weights_bf16(w, s, N, K)
             if decode:
                 hip.gemv(x, wb, rows, N, K, epi, ep, ws=ws)

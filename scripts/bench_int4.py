@@ -10,6 +10,10 @@
   kernel (up to 64 rows), the best cooperative fp8 config and dequantise + bf16, by the same method.
 --steps: ms per token of a random-init model (default llama2-7b) at batch 1, 16, 64 and 128, one captured
   decode graph per weight dtype, the dtypes alternated window by window in one process.
+--gemm: the W4A16 GEMM (csrc/quant/gemm_int4.hip) at 256, 512 and 2048 rows against dequantise + the
+  bf16 GEMM (hip.gemm) on the same operands, by the same method; every K split is timed once first.
+--gemm-step: a captured 512-row int4 decode step of --layers Llama-2-7B layers, LSA_INT4_GEMM=1
+  against =0 (the dequantising route), one engine each, alternated window by window.
 One JSON line per result; everything is also written to --out."""
 import argparse
 import json
@@ -178,11 +182,107 @@ def steps(model: str, batches, windows: int, n_steps: int, out: list) -> None:
         out.append(line)
 
 
+def gemm(model: str, rows_list, windows: int, out: list) -> None:
+    from llm_sharding_amd.config import llama2_7b
+    from llm_sharding_amd.models.rope import rope_table
+    cos, sin = rope_table(llama2_7b(), 1024, DEV)
+    cws, sk_ws = hip.CoopWorkspace(DEV, slab_floats=1 << 25), hip.SkWorkspace(DEV)
+    for name, (N, K) in MODEL_SHAPES[model].items():
+        epi = EPIS[name]
+        if epi == hip.EPI_ARGMAX:
+            continue
+        q4, s4 = int4.quantize_int4_groups(torch.randn(N, K, device=DEV).mul_(0.02))
+        p4, s4 = int4.pack_b_int4(q4), int4.pack_scales_int4(s4)
+        nb = max(2, (600 << 20) // int4.int4_bytes(N, K) + 1)
+        w4, sc4 = [p4.clone() for _ in range(nb)], [s4.clone() for _ in range(nb)]
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device=DEV)
+        del q4
+        for M in rows_list:
+            x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+            o = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
+            nh, nkv = MODEL_HEADS[model] if epi == hip.EPI_QKV else (1, 1)
+            qb = torch.zeros(M, max(N, 128), dtype=torch.bfloat16, device=DEV)
+            kc = torch.zeros(M, nkv, 1024, 128, dtype=torch.bfloat16, device=DEV)
+            slot = torch.arange(M, dtype=torch.int32, device=DEV)
+            pos = torch.full((M,), 100, dtype=torch.int32, device=DEV)
+            if epi == hip.EPI_QKV:
+                ep = hip.make_epi(out=qb, k_cache=kc, v_cache=kc, slot=slot, pos=pos, cos=cos, sin=sin, ldo=qb.shape[1],
+                                  n_heads=nh, n_kv=nkv, head_dim=128, t_max=1024)
+            else:
+                ep = hip.make_epi(out=o, resid=o, ldo=N, ldr=N)
+
+            def fg(cfg):
+                return lambda i: int4.gemm_int4(x, w4[i % nb], sc4[i % nb], M, N, K, epi, ep, ws=cws, cfg=cfg)
+
+            def fdq(i):  # the route without the native GEMM: dequantise, then the bf16 GEMM
+                hip.gemm(x, int4.dequant_int4_packed(w4[i % nb], sc4[i % nb], scratch, N, K), M, N, K, epi, ep, ws=cws,
+                         sk_ws=sk_ws)
+
+            cg = sorted((timeit(fg(c)), c) for c in int4.int4_gemm_candidates(M, N, K, epi)
+                        if int4.int4_gemm_slab_floats(M, N, c[1]) <= cws.slab.numel())
+            auto = int4.int4_gemm_config(M, N, K, epi, cws.slab.numel(), cws.counters.numel())
+            fns = {"gemm_int4": fg(cg[0][1]), "dequant+bf16": fdq}
+            if auto != cg[0][1]:
+                fns["gemm_int4_auto"] = fg(auto)
+            r = _windows(fns, windows)
+            line = {"table": "gemm", "shape": name, "N": N, "K": K, "M": M, "gemm_int4_cfg": list(cg[0][1]),
+                    "gemm_int4_auto_cfg": list(auto), "gemm_int4_sweep": [(round(t, 2),) + tuple(c) for t, c in cg]}
+            for k, (us, spread) in r.items():
+                line[k + "_us"], line[k + "_spread"] = round(us, 2), round(spread, 3)
+            print(json.dumps(line), flush=True)
+            out.append(line)
+        del w4, sc4, scratch
+        torch.cuda.empty_cache()
+
+
+def gemm_step(model: str, layers: int, rows: int, windows: int, n_steps: int, out: list) -> None:
+    from llm_sharding_amd.config import get_preset
+    from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource
+    from llm_sharding_amd.runtime.engine_int4 import make_stage_engine
+    cfg = get_preset(model)
+    graphs = {}
+    for flag in ("1", "0"):  # the switch is read when the engine allocates and when the graph is captured
+        os.environ["LSA_INT4_GEMM"] = flag
+        e = make_stage_engine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                              max_slots=rows, max_seq=256, max_prefill_rows=rows, weight_dtype="int4")
+        for s in range(rows):
+            e.seq_len[s] = 128
+        graphs[flag] = DecodeGraph(e, rows, "full", slots=list(range(rows))).capture()
+    del os.environ["LSA_INT4_GEMM"]
+
+    def run(g):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        g.set_positions()
+        g.replay()
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(n_steps):
+            g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n_steps
+
+    t = {f: [] for f in graphs}
+    for _ in range(windows):
+        for f, g in graphs.items():
+            t[f].append(run(g))
+    line = {"table": "gemm_step", "model": model, "layers": layers, "rows": rows, "steps_per_window": n_steps, "windows": windows}
+    for f, name in (("1", "native"), ("0", "dequant")):
+        line[name + "_ms"] = round(statistics.median(t[f]), 4)
+        line[name + "_spread"] = round((max(t[f]) - min(t[f])) / statistics.median(t[f]), 3)
+    print(json.dumps(line), flush=True)
+    out.append(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--coop", action="store_true", help="the cooperative int4 kernel's table (rows 17..128)")
     ap.add_argument("--steps", action="store_true")
+    ap.add_argument("--gemm", action="store_true", help="the int4 GEMM's table (rows above 128, prefill chunks)")
+    ap.add_argument("--gemm-rows", default="256,512,2048")
+    ap.add_argument("--gemm-step", action="store_true", help="captured 512-row int4 decode step, native GEMM on / off")
+    ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--rows", default="1,16,64")
     ap.add_argument("--coop-rows", default="32,64,96,128")
@@ -197,6 +297,10 @@ def main():
         kernels(a.model, [int(r) for r in a.rows.split(",")], a.windows, out)
     if a.coop:
         kernels(a.model, [int(r) for r in a.coop_rows.split(",")], a.windows, out, coop=True)
+    if a.gemm:
+        gemm(a.model, [int(r) for r in a.gemm_rows.split(",")], a.windows, out)
+    if a.gemm_step:
+        gemm_step(a.model, a.layers, 512, a.windows, a.n_steps, out)
     if a.steps:
         steps(a.model, [int(b) for b in a.batches.split(",")], a.windows, a.n_steps, out)
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
