@@ -66,9 +66,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "reserves prompt + --max-new-tokens at admission")
     ap.add_argument("--kv-pages", type=int, default=0,
                     help="with --kv-layout paged: pages in the pool (0: one sequence of max_seq tokens, plus the null page)")
-    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
-                    help="projection weights on the GPU: bf16, fp8 (OCP e4m3, per-row scales, fp8 lm_head) or int4 "
-                         "(symmetric group-128, bf16 lm_head); ignored on the CPU")
+    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8", "int4", "mxfp4"),
+                    help="projection weights on the GPU: bf16, fp8 (OCP e4m3, per-row scales, fp8 lm_head), int4 "
+                         "(symmetric group-128, bf16 lm_head) or mxfp4 (OCP e2m1 with e8m0 block-32 scales, fp8 "
+                         "activations in decode, bf16 lm_head); ignored on the CPU")
     ap.add_argument("--hf-compare", default="", help="HF checkpoint dir: also run transformers' greedy generate "
                                                      "(the reference inference.py's path, fp32 CPU) and compare tokens")
     ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy decode")
@@ -111,7 +112,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "lookup; --spec-ngram is ignored then")
     ap.add_argument("--draft-random", default="", metavar="PRESET",
                     help="with --speculative: a random-init draft model (seed 1) of preset PRESET, beside --random")
-    ap.add_argument("--draft-weight-dtype", default="bf16", choices=("bf16", "fp8", "int4"),
+    ap.add_argument("--draft-weight-dtype", default="bf16", choices=("bf16", "fp8", "int4", "mxfp4"),
                     help="the draft model's projection weights on the GPU")
     return ap
 

@@ -326,6 +326,11 @@ def stage_memory(cfg: LlamaConfig, n_layers: int, *, slots: int, max_seq: int, p
         shapes = [(cfg.qkv_size, H), (H, cfg.q_size), (cfg.mlp_in_size, H), (H, cfg.intermediate_size)]
         w += n_layers * sum(int4.int4_bytes(n, k) - n * k * elem_bytes for n, k in shapes)
         w_scratch = scratch_sets * 2 * max(n * k for n, k in shapes)
+    if weight_dtype == "mxfp4":  # e2m1 codes + one e8m0 byte per 32 weights, and the same bf16 buffer
+        from ..ops import mx4
+        shapes = [(cfg.qkv_size, H), (H, cfg.q_size), (cfg.mlp_in_size, H), (H, cfg.intermediate_size)]
+        w += n_layers * sum(mx4.mx4_bytes(n, k) - n * k * elem_bytes for n, k in shapes)
+        w_scratch = scratch_sets * 2 * max(n * k for n, k in shapes)
     if has_embed:
         w += cfg.vocab_size * H * elem_bytes
     if head_rows:

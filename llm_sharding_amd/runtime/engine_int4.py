@@ -292,6 +292,9 @@ def make_stage_engine(cfg, start: int, end: int, device="cpu", dtype=torch.bfloa
         return Fp8KVStageEngine(cfg, start, end, device, dtype, weight_dtype=weight_dtype, **kw)
     if weight_dtype == "int4":
         return Int4StageEngine(cfg, start, end, device, dtype, **kw)
+    if weight_dtype == "mxfp4":  # MXFP4 weights, W4A8 decode (runtime/engine_mx4.py)
+        from .engine_mx4 import Mx4StageEngine
+        return Mx4StageEngine(cfg, start, end, device, dtype, **kw)
     if torch.device(device).type == "cuda":
         # the default dtypes on a GPU: StageEngine plus the gemm_skp route of the residual
         # projections at 385..512 decode rows (runtime/engine_skp.py; LSA_GEMM_SKP=0 turns it off)

@@ -249,3 +249,5 @@ def check_kv_dtype(kv_dtype: str, weight_dtype: str = "bf16") -> None:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
     if kv_dtype == "fp8" and weight_dtype == "int4":
         raise ValueError("kv_dtype='fp8' with weight_dtype='int4' is not built: use bf16 or fp8 weights")
+    if kv_dtype == "fp8" and weight_dtype == "mxfp4":
+        raise ValueError("kv_dtype='fp8' with weight_dtype='mxfp4' is not built: use bf16 or fp8 weights")

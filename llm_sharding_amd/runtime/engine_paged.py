@@ -319,6 +319,9 @@ def check_kv_layout(kv_layout: str, kv_pages=None, weight_dtype: str = "bf16", k
     if weight_dtype == "int4":
         raise ValueError("kv_layout='paged' with weight_dtype='int4' is not built: int4 weights have a forward body "
                          "of their own (runtime/engine_int4.py)")
+    if weight_dtype == "mxfp4":
+        raise ValueError("kv_layout='paged' with weight_dtype='mxfp4' is not built: mxfp4 weights have a forward "
+                         "body of their own (runtime/engine_mx4.py)")
     if kv_dtype != "bf16":
         raise ValueError(f"kv_layout='paged' holds bf16 pages: kv_dtype={kv_dtype!r} together with paged is not built")
     if kv_pages is not None and int(kv_pages) < 2:
