@@ -89,7 +89,9 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     # gemm_int4.hip: the same, for its group fold and split-K combine.
     # gemv_mx4.hip: the same, for its activation quantiser and split-K combine.
-    extra_flags = {"kv8_mfma.hip": no_pk, "gemv_coop_int4.hip": no_pk, "gemm_int4.hip": no_pk, "gemv_mx4.hip": no_pk}
+    # gemm_mx4.hip: the same, for its pre-pass quantiser and split-K combine.
+    extra_flags = {"kv8_mfma.hip": no_pk, "gemv_coop_int4.hip": no_pk, "gemm_int4.hip": no_pk, "gemv_mx4.hip": no_pk,
+                   "gemm_mx4.hip": no_pk}
     jobs_list = []
     kobjs = []
     for s in kernel_srcs:

@@ -28,6 +28,7 @@
 //  * A workgroup's last waves may own tiles past N / 16 (any tile count is served): they run on a
 //    clamped tile and their results are dropped.
 #include "../kernels/epilogue.h"
+#include "mx8_quant.h"
 
 #include <utility>
 
@@ -39,13 +40,6 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 template <int... S, typename F>
 LSA_DEVICE bool static_all(std::integer_sequence<int, S...>, F&& f) {
   return (f(std::integral_constant<int, S>{}) && ...);
-}
-
-// 4 fp32 -> one dword of e4m3 codes (round to nearest even)
-LSA_DEVICE unsigned pack4_fp8(const float* y) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-  return (unsigned)w;
 }
 
 template <int MB, int TNW, int NW, int EPI, bool NORM>
@@ -126,21 +120,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_mx4_kernel(
         for (int j = 0; j < 8; ++j) q += f[j] * f[j];
         ss[i] += count * q;
       }
-      float amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
-      amax = fmaxf(amax, dpp_mov<0xB1>(amax));  // quad_perm [1,0,3,2]
-      amax = fmaxf(amax, dpp_mov<0x4E>(amax));  // quad_perm [2,3,0,1]
-      int e = (int)(__float_as_uint(amax) >> 23);
-      e = (e < 8 ? 8 : e) - 7;
-      if (amax == 0.f) e = 127;
-      const float inv = __uint_as_float((unsigned)(254 - e) << 23);
-      float y[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) y[j] = f[j] * inv;
       u32x2_t c;
-      c[0] = pack4_fp8(y);
-      c[1] = pack4_fp8(y + 4);
+      const int e = mx8_quant_quad(f, c);
       *reinterpret_cast<u32x2_t*>(ab + a_dst[i]) = c;
       if (asub == 0) {
         const int p = i * NW + w;

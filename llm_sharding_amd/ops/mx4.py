@@ -1,6 +1,8 @@
 """MXFP4 weights (W4A8 decode): the OCP microscaling format, its packed layout for the gfx950
 block-scaled MFMA, the activation quantiser's contract, the kernel's configs and bindings
-(csrc/quant/gemv_mx4.hip) and the dispatcher :func:`proj_mx4`.
+(csrc/quant/gemv_mx4.hip) and the dispatcher :func:`proj_mx4`; at the end, the activation image,
+configs and bindings of the opt-in GEMM for more than 128 rows (csrc/quant/gemm_mx4.hip,
+:func:`proj_gemm_mx4`).
 
 Weights. Each fused, norm-folded projection ``W[N, K]`` is cut along K into blocks of 32; a block
 is one e8m0 exponent byte ``e`` (scale ``2^(e - 127)``) and 32 e2m1 codes (sign bit 8, magnitudes
@@ -31,6 +33,7 @@ the bf16 decode path's full-depth fixture."""
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional
 
 import torch
@@ -211,6 +214,12 @@ def _lib():
         L.lsa_gemv_mx4.argtypes = [vp, i, vp, vp, vp, i, i, i, i, f, i, ctypes.POINTER(hip.EpiArgs), i, i, i, vp, vp, vp]
         L.lsa_dequant_mx4_packed.argtypes = [vp, vp, vp, i, i, vp]
         L.lsa_gemv_mx4.restype = L.lsa_dequant_mx4_packed.restype = i
+        if not hasattr(L, "lsa_gemm_mx4"):
+            raise RuntimeError("the kernel library has no lsa_gemm_mx4: rebuild it (python csrc/build.py)")
+        L.lsa_quant_act_mx8.argtypes = [vp, i, vp, vp, vp, i, i, vp]
+        L.lsa_gemm_mx4.argtypes = [vp, vp, vp, vp, i, i, i, i, ctypes.POINTER(hip.EpiArgs), i, i, vp, ctypes.c_longlong, vp,
+                                   i, vp]
+        L.lsa_quant_act_mx8.restype = L.lsa_gemm_mx4.restype = i
         _L = L
     return _L
 
@@ -280,3 +289,171 @@ def dequant_mx4_packed(wq: torch.Tensor, scales: torch.Tensor, out: torch.Tensor
     hip._check(_lib().lsa_dequant_mx4_packed(hip._p(wq), hip._p(scales), hip._p(out), N, K, hip._stream()),
                "lsa_dequant_mx4_packed")
     return out.view(-1)[:N * K].view(N // 16, K // 32, 64, 8)
+
+
+# ------------------------------------------------------------------------------ the GEMM (prefill, > 128 rows)
+# csrc/quant/gemm_mx4.hip. The activations are quantised ONCE per projection input by a pre-pass
+# (lsa_quant_act_mx8, exactly quantize_act_mx8) into the image the MFMA's A operand wants:
+# * codes ``A8[ceil(M/16)][K/128][2 halves][64 lanes][16 B]``: element k of a K-step sits in half
+#   ``k // 64``, lane ``16 * ((k % 64) // 16) + row``, byte ``k % 16`` - a row block's K-step is
+#   2 KiB contiguous, and two ds_read_b128 per lane are the operand;
+# * exponents ``EA[ceil(M/16)][ceil(K/512)][64 lanes]`` dwords: byte ``i`` of lane ``16 b + row`` is
+#   the e8m0 byte of 32-block ``b`` in K-step ``4 g + i`` (127 past K), picked by ``op_sel`` as the
+#   weight scales are: the GEMM reads one dword per row block and FOUR K-steps, straight into a
+#   register (the ISA takes scale_a from a VGPR byte, so the exponents never pass through LDS);
+# * rows >= M of the last row block: zero codes, exponent 127.
+# (bn, depth) instantiated in gemm_mx4.hip - keep in sync. bn 256 is not built: its SwiGLU and QKV
+# instantiations needed 36 bytes of scratch per lane (the kernel's header has the compiler's report).
+MX4_GEMM_CONFIGS = [(128, 4)]
+MX4_GEMM_SPLITS = (1, 2, 4, 8)
+MX4_GEMM_ROWS = 128       # rows of an output tile
+# workgroups from which a further K split measured no faster: 192 reproduces the fastest split of
+# every shape and row count of profiles/mx4.md "GEMM above 128 rows" (qkv at 256 rows, 192 tiles,
+# is fastest unsplit; 64 / 128 tiles want 4 / 2 splits). Every measured shape beat dequantise + bf16
+# by more than the spread, so with the switch on no shape is routed back.
+MX4_GEMM_MIN_GRID = 192
+
+
+def a_image_bytes(M: int, K: int) -> tuple:
+    """(code bytes, exponent bytes) of the MXFP8 image of ``M`` rows x ``K``."""
+    rb = -(-M // 16)
+    return rb * 16 * K, rb * scale_groups(K) * 256
+
+
+def pack_a_mx8(x: torch.Tensor) -> tuple:
+    """bf16 [M, K] (K % 128 == 0) -> (A8 uint8 flat, EA uint8 flat): :func:`quantize_act_mx8` in the
+    pre-pass's layout, the padded rows included."""
+    M, K = x.shape
+    if K % MX_STEP or K < MX_STEP:
+        raise ValueError(f"pack_a_mx8 needs K % {MX_STEP} == 0, got K={K}")
+    codes, e = quantize_act_mx8(x)
+    rb, ks, ng = -(-M // 16), K // MX_STEP, scale_groups(K)
+    cp = torch.zeros(rb * 16, K, dtype=torch.uint8, device=x.device)
+    cp[:M] = codes
+    ep = torch.full((rb * 16, 4 * ng, 4), 127, dtype=torch.uint8, device=x.device)
+    ep[:M, :ks] = e.view(M, ks, 4)
+    a8 = cp.view(rb, 16, ks, 2, 4, 16).permute(0, 2, 3, 4, 1, 5).reshape(-1)  # [rb][step][half][group][row][byte]
+    ea = ep.view(rb, 16, ng, 4, 4).permute(0, 2, 4, 1, 3).reshape(-1)        # [rb][g][block][row][i]
+    return a8, ea
+
+
+def _row_tiles(M: int) -> int:
+    return -(-M // MX4_GEMM_ROWS)
+
+
+def mx4_gemm_slab_floats(M: int, N: int, sk: int) -> int:
+    """fp32 workspace a split mxfp4 GEMM launch needs: sk partial tiles of whole 128-row tiles
+    (0 when sk == 1)."""
+    return 0 if sk <= 1 else sk * _row_tiles(M) * MX4_GEMM_ROWS * N
+
+
+def mx4_gemm_candidates(M: int, N: int, K: int, epi: int = 0) -> list:
+    """(bn, sk) the mxfp4 GEMM can run: bn divides N, every K split keeps a 512-k scale group, the
+    partial slab stays under 2 GiB."""
+    if M < 1 or N < 1 or K < MX_STEP or K % MX_STEP or N * K // 2 >= 1 << 31 \
+            or epi not in (hip.EPI_STORE, hip.EPI_RESID, hip.EPI_SWIGLU, hip.EPI_QKV):
+        return []
+    return [(bn, sk) for bn, _ in MX4_GEMM_CONFIGS if N % bn == 0 for sk in MX4_GEMM_SPLITS
+            if sk <= scale_groups(K) and 4 * mx4_gemm_slab_floats(M, N, sk) < 1 << 31]
+
+
+def mx4_gemm_config(M: int, N: int, K: int, epi: int = 0, slab_floats: Optional[int] = None,
+                    counters: Optional[int] = None) -> Optional[tuple]:
+    """(bn, sk) or None when no built tile divides N or nothing fits the workspace. The fewest K
+    splits that give at least MX4_GEMM_MIN_GRID workgroups (every split writes and the last
+    arriver re-reads an fp32 tile); where no split reaches that grid, the most splits."""
+    cands = [(bn, sk) for bn, sk in mx4_gemm_candidates(M, N, K, epi)
+             if (slab_floats is None or mx4_gemm_slab_floats(M, N, sk) <= slab_floats)
+             and (counters is None or sk == 1 or _row_tiles(M) * (N // bn) <= counters)]
+    if not cands:
+        return None
+
+    def cost(c):
+        bn, sk = c
+        grid = _row_tiles(M) * (N // bn) * sk
+        return (grid < MX4_GEMM_MIN_GRID, sk if grid >= MX4_GEMM_MIN_GRID else -sk)
+    return min(cands, key=cost)
+
+
+def quant_act_mx8(x: torch.Tensor, M: int, K: int, scratch: torch.Tensor, a_rows: Optional[torch.Tensor] = None) -> tuple:
+    """The pre-pass: rows of bf16 ``x`` [>=M, >=K] (16-byte aligned; gathered through ``a_rows`` if
+    given) -> (A8, EA) views of the uint8 ``scratch``, which must hold ``sum(a_image_bytes(M, K))``."""
+    nc, ne = a_image_bytes(M, K)
+    hip._req(M >= 1 and K >= MX_STEP and K % MX_STEP == 0, f"quant_act_mx8: K % {MX_STEP}")
+    hip._req(hip._is_bf16_cuda(x) and x.dim() == 2 and x.shape[1] >= K and x.stride(1) == 1 and x.data_ptr() % 16 == 0
+             and x.stride(0) % 8 == 0, "quant_act_mx8: x must be bf16 [rows, >=K] row-major with 16-byte aligned rows")
+    if a_rows is None:
+        hip._req(x.shape[0] >= M, "quant_act_mx8: x has fewer rows than M")
+    else:
+        hip._req(a_rows.dtype == torch.int32 and a_rows.is_cuda and a_rows.numel() >= M, "quant_act_mx8: a_rows")
+    hip._req(scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= nc + ne
+             and scratch.data_ptr() % 16 == 0, f"quant_act_mx8: scratch of {nc + ne} uint8 bytes, 16-byte aligned")
+    a8, ea = scratch.view(-1)[:nc], scratch.view(-1)[nc:nc + ne]
+    hip._check(_lib().lsa_quant_act_mx8(hip._p(x), x.stride(0), hip._p(a_rows), hip._p(a8), hip._p(ea), M, K, hip._stream()),
+               "lsa_quant_act_mx8")
+    return a8, ea
+
+
+def gemm_mx4(a8: torch.Tensor, ea: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, M: int, N: int, K: int,
+             epi: int, ep: hip.EpiArgs, ws: Optional[hip.CoopWorkspace] = None, cfg: Optional[tuple] = None) -> None:
+    """W4A8 GEMM (csrc/quant/gemm_mx4.hip), any M >= 1: (``a8``, ``ea``) the pre-pass image of the
+    activations, ``wq`` / ``scales`` as for :func:`gemv_mx4`. ``cfg`` = (bn, sk), default
+    :func:`mx4_gemm_config`; ``ws``: the split-K slab and arrival counters. The fused-RMSNorm fields
+    of ``ep`` as in ``hip.gemm_sk``: ``ss_in`` (QKV / SWIGLU, K == 64 ss_n), ``ss_out`` (RESID)."""
+    hip._req(M >= 1, f"gemm_mx4 needs at least one row, got {M}")
+    hip._req(epi in (hip.EPI_STORE, hip.EPI_RESID, hip.EPI_SWIGLU, hip.EPI_QKV), f"gemm_mx4: epilogue {epi} not built")
+    hip._check_epi(epi, ep, N)
+    _check_weights(wq, scales, N, K, "gemm_mx4")
+    nc, ne = a_image_bytes(M, K)
+    hip._req(a8.is_cuda and a8.dtype == torch.uint8 and a8.is_contiguous() and a8.numel() >= nc and a8.data_ptr() % 16 == 0
+             and ea.is_cuda and ea.dtype == torch.uint8 and ea.is_contiguous() and ea.numel() >= ne and ea.data_ptr() % 4 == 0,
+             f"gemm_mx4: the activation image needs {nc} code and {ne} exponent bytes, 16-byte aligned (quant_act_mx8)")
+    hip._req(not ep.ss_in or (epi in (hip.EPI_QKV, hip.EPI_SWIGLU) and K == 64 * ep.ss_n and ep.ss_n % 4 == 0),
+             "gemm_mx4: ss_in needs a QKV / SWIGLU epilogue and K == 64 ss_n")
+    hip._req(not ep.ss_out or (epi == hip.EPI_RESID and N == 64 * ep.ss_n), "gemm_mx4: ss_out needs a RESID epilogue and N == 64 ss_n")
+    hip._req(epi != hip.EPI_SWIGLU or not ep.bias, "gemm_mx4: no bias on the SwiGLU epilogue")
+    if ws is None:
+        ws = hip.default_workspace(wq.device)
+    if cfg is None:
+        cfg = mx4_gemm_config(M, N, K, epi, ws.slab.numel(), ws.counters.numel())
+        hip._req(cfg is not None, f"gemm_mx4: no config for N={N} K={K} M={M}")
+    cfg = tuple(cfg)
+    hip._req(cfg in mx4_gemm_candidates(M, N, K, epi), f"gemm_mx4: config {cfg} not built or invalid for N={N} K={K} M={M}")
+    bn, sk = cfg
+    need = mx4_gemm_slab_floats(M, N, sk)
+    hip._req(ws.slab.numel() >= need, f"gemm_mx4: workspace too small ({ws.slab.numel()} < {need} floats)")
+    hip._req(sk == 1 or ws.counters.numel() >= _row_tiles(M) * (N // bn), "gemm_mx4: workspace counters too small")
+    rc = _lib().lsa_gemm_mx4(hip._p(a8), hip._p(ea), hip._p(wq), hip._p(scales), M, N, K, epi, ctypes.byref(ep), bn, sk,
+                            hip._p(ws.slab), ws.slab.numel(), hip._p(ws.counters), ws.counters.numel(), hip._stream())
+    hip._check(rc, "lsa_gemm_mx4")
+
+
+def mx4_gemm_enabled() -> bool:
+    """The run-time switch, read at every call: ``LSA_MX4_GEMM=1`` routes prefill chunks and decode
+    batches above 128 rows to the native GEMM. Off by default: it makes those rows W4A8 (MXFP8
+    activations), a numerics change a user chooses; the default keeps the bits of the bf16 kernels
+    on the dequantised weights (tests/test_mx4_gpu.py)."""
+    return os.environ.get("LSA_MX4_GEMM", "0") == "1"
+
+
+def proj_gemm_mx4(x: torch.Tensor, wq: torch.Tensor, scales: Optional[torch.Tensor], M: int, N: int, K: int, epi: int,
+                  ep: hip.EpiArgs, ws: Optional[hip.CoopWorkspace] = None, a_scratch: Optional[torch.Tensor] = None) -> bool:
+    """A prefill chunk or a decode batch above 128 rows on the native mxfp4 GEMM: the pre-pass into
+    ``a_scratch``, then :func:`gemm_mx4`. False (nothing launched) where the weights are not mxfp4,
+    the switch is off, there is no scratch for the image or no config serves the shape: the caller
+    dequantises."""
+    if scales is None or a_scratch is None or not mx4_gemm_enabled() or sum(a_image_bytes(M, K)) > a_scratch.numel():
+        return False
+    w = ws if ws is not None else hip.default_workspace(x.device)
+    cfg = mx4_gemm_config(M, N, K, epi, w.slab.numel(), w.counters.numel())
+    if cfg is None:
+        return False
+    a8, ea = quant_act_mx8(x, M, K, a_scratch)
+    gemm_mx4(a8, ea, wq, scales, M, N, K, epi, ep, ws=w, cfg=cfg)
+    return True
+
+
+def mx4_gemm_serves(shapes, rows: int, slab_floats: Optional[int] = None, counters: Optional[int] = None) -> bool:
+    """Whether :func:`proj_gemm_mx4` takes every (N, K) of ``shapes`` at ``rows`` rows."""
+    return mx4_gemm_enabled() and all(mx4_gemm_config(rows, n, k, hip.EPI_STORE, slab_floats, counters) is not None
+                                      for n, k in shapes)

@@ -7,7 +7,11 @@ microscaling fp4: e2m1 codes with one e8m0 exponent per 32 weights along K, 4.25
 quantises the activations to MXFP8 on the way and multiplies on the block-scaled MFMA: decode is
 W4A8. Larger decode batches and prefill chunks dequantise one projection at a time into
 ``w_scratch`` (exactly: every ``code * 2^e`` is a bf16 value) and run the bf16 kernels on the
-routes fp8 weights take: they are W4A16 on the same weights.
+routes fp8 weights take: they are W4A16 on the same weights. With ``LSA_MX4_GEMM=1`` (read at
+construction for the scratch, at every call for the route) those rows run csrc/quant/gemm_mx4.hip
+instead: a pre-pass quantises each projection's input to MXFP8 once into ``a_mx8`` and the GEMM
+multiplies on the block-scaled MFMA, so prefill becomes W4A8 too (``mx4.proj_gemm_mx4``; the
+residual projections on its EPI_RESID epilogue, no ``part_k``, when all four shapes qualify).
 
 The lm_head, the embedding and the norms stay bf16. Each fused matrix is quantised here with its
 RMSNorm weight folded in. Llama-family layers only: GPT-2 raises ``NotImplementedError``. The fp8
@@ -58,10 +62,39 @@ class Mx4StageEngine(StageEngine):
         return out
 
     def _alloc_runtime(self) -> None:
+        # the MXFP8 image of one projection's input (codes + exponents, ops/mx4.py) for the native
+        # GEMM: allocated only when LSA_MX4_GEMM is on at construction
+        self.a_mx8 = None
+        R = max(self.max_prefill_rows, self.DECODE_MAX_ROWS)
+        if self.mx4 and mx4.mx4_gemm_enabled() and R > mx4.MX4_MAX_ROWS:
+            kmax = max(k for _, k in self.proj_shapes(self.cfg))
+            self.a_mx8 = torch.empty(sum(mx4.a_image_bytes(R, kmax)), dtype=torch.uint8, device=self.device)
         super()._alloc_runtime()
         if self.mx4:  # one projection's bf16 weights, for the > 128-row and prefill paths
             shapes = self.proj_shapes(self.cfg)
             self.w_scratch = torch.empty(max(n * k for n, k in shapes), dtype=torch.bfloat16, device=self.device)
+
+    def _alloc_part_k(self, R: int):
+        """No split-K partial buffer where the native mxfp4 GEMM takes all four projections at every
+        row count up to ``R``: the residual projections then run its EPI_RESID (+ ss_out) epilogue."""
+        ws = self.coop_ws
+        if self.a_mx8 is not None and all(
+                mx4.mx4_gemm_serves(self.proj_shapes(self.cfg), m, ws.slab.numel(), ws.counters.numel())
+                for m in range(mx4.MX4_GEMM_ROWS, R + 1, mx4.MX4_GEMM_ROWS)):
+            return None
+        return super()._alloc_part_k(R)
+
+    # a forward pass also writes the activation image: one per concurrently running graph
+    SCRATCH_ATTRS = StageEngine.SCRATCH_ATTRS + ("a_mx8",)
+
+    def decode_scratch(self, k: int, rows: Optional[int] = None) -> dict:
+        d = super().decode_scratch(k, rows)
+        if "a_mx8" not in d:
+            d["a_mx8"] = None if self.a_mx8 is None else torch.empty_like(self.a_mx8)
+        return d
+
+    def memory_bytes(self) -> int:
+        return super().memory_bytes() + (0 if self.a_mx8 is None else self.a_mx8.numel())
 
     # ------------------------------------------------------------------------- HIP path
     # _forward_hip is StageEngine's, statement for statement, with the weight closures (wbf, dec)
@@ -112,6 +145,7 @@ class Mx4StageEngine(StageEngine):
             hip.resid_rmsnorm_partials(hbuf, part, pc[3], rows, eps)
 
         def pre(x, w, s, N, K, epi, ep):
+            if mx4.proj_gemm_mx4(x, w, s, rows, N, K, epi, ep, ws=ws, a_scratch=self.a_mx8): return  # else dequantise
             hip.gemm(x, wbf(w, s, N, K), rows, N, K, epi, ep, ws=ws, sk_ws=self.sk_ws)
 
         # residual projections as split-K partials summed by the next norm kernel, where measured

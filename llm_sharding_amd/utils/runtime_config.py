@@ -46,6 +46,8 @@ KNOBS = {
     "LSA_GEMM_SKP_TUNING": ("env", "diagnostic", "", "path of another gemm_skp tuning table (ops/skp_tuning.txt)"),
     "LSA_INT4_GEMM": ("env", "product", "0", "1 = the int4 engine runs shapes of up to 64 output tiles above 128 rows "
                       "and in prefill on the native int4 GEMM instead of dequantise + bf16 GEMM (profiles/int4.md)"),
+    "LSA_MX4_GEMM": ("env", "product", "0", "1 = the mxfp4 engine runs prefill chunks and decode batches above 128 rows "
+                     "on the native W4A8 GEMM (MXFP8 activations) instead of dequantise + bf16 GEMM (profiles/mx4.md)"),
     "LSA_ATTN_MIN_CHUNK": ("env", "diagnostic", "256", "shortest split-KV chunk in keys"),
     "LSA_ATTN_MFMA": ("env", "diagnostic", "1", "0 = no MFMA GQA decode kernel"),
     "LSA_ATTN_MFMA_MIN_ITEMS": ("env", "diagnostic", "512", "rows x kv-heads from which GQA decode uses MFMA"),

@@ -8,6 +8,10 @@
 --steps: ms per token of a random-init model (default llama2-7b, optionally the first --layers
   layers) at batch 1, 16, 64 and 128, one captured decode graph per weight dtype, the dtypes
   alternated window by window in one process.
+--gemm: the W4A8 GEMM (csrc/quant/gemm_mx4.hip) at 256 .. 2048 rows: the pre-pass alone, pre-pass +
+  GEMM at every built config, dequantise + hip.gemm and hip.gemm on bf16 weights, with TFLOP/s.
+--gemm-step: a captured 512-row decode step of --layers layers and one 2048-token prefill,
+  LSA_MX4_GEMM=1 against =0, one engine each, alternated window by window.
 One JSON line per result; everything is also written to --out."""
 import argparse
 import json
@@ -132,10 +136,116 @@ def steps(model: str, batches, windows: int, n_steps: int, layers: int, out: lis
         out.append(line)
 
 
+def gemm(model: str, rows_list, windows: int, out: list) -> None:
+    """Per projection shape and row count (STORE epilogue): the pre-pass alone, pre-pass + gemm_mx4
+    at every built config against the chooser's, dequantise + hip.gemm (the default route) and
+    hip.gemm on bf16 weights; TFLOP/s = 2 M N K / time."""
+    cws, sk = hip.CoopWorkspace(DEV, slab_floats=1 << 27), hip.SkWorkspace(DEV)
+    for name, (N, K) in MODEL_SHAPES[model].items():
+        if EPIS[name] == hip.EPI_ARGMAX:
+            continue
+        w = torch.randn(N, K, device=DEV).mul_(0.02)
+        qm, em = mx4.quantize_mx4(w)
+        wm, scm = mx4.pack_b_mx4(qm), mx4.pack_scales_mx4(em)
+        wb = packing.pack_b(w.to(torch.bfloat16))
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device=DEV)
+        del w, qm
+        for M in rows_list:
+            x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+            o = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
+            ep, epi = hip.make_epi(out=o, ldo=N), hip.EPI_STORE
+            img = torch.empty(sum(mx4.a_image_bytes(M, K)), dtype=torch.uint8, device=DEV)
+
+            def fg(cfg):
+                return lambda i: mx4.gemm_mx4(*mx4.quant_act_mx8(x, M, K, img), wm, scm, M, N, K, epi, ep, ws=cws, cfg=cfg)
+
+            cands = [c for c in mx4.mx4_gemm_candidates(M, N, K, epi) if mx4.mx4_gemm_slab_floats(M, N, c[1]) <= cws.slab.numel()]
+            auto = mx4.mx4_gemm_config(M, N, K, epi, cws.slab.numel(), cws.counters.numel())
+            fns = {f"mx4_bn{c[0]}_sk{c[1]}": fg(c) for c in cands}
+            fns.update({"prepass": lambda i: mx4.quant_act_mx8(x, M, K, img),
+                        "dequant+bf16": lambda i: hip.gemm(x, mx4.dequant_mx4_packed(wm, scm, scratch, N, K), M, N, K, epi, ep,
+                                                           ws=cws, sk_ws=sk),
+                        "bf16": lambda i: hip.gemm(x, wb, M, N, K, epi, ep, ws=cws, sk_ws=sk)})
+            r = _windows(fns, windows)
+            line = {"table": "gemm", "shape": name, "N": N, "K": K, "M": M, "auto_cfg": list(auto)}
+            for k, (us, spread) in r.items():
+                line[k + "_us"], line[k + "_spread"] = round(us, 2), round(spread, 3)
+                if k != "prepass":
+                    line[k + "_TFLOPs"] = round(2.0 * M * N * K / us / 1e6, 1)
+            print(json.dumps(line), flush=True)
+            out.append(line)
+        del wm, scm, wb, scratch
+        torch.cuda.empty_cache()
+
+
+def gemm_step(model: str, layers: int, rows: int, prefill: int, windows: int, n_steps: int, out: list) -> None:
+    """LSA_MX4_GEMM=1 against =0, one engine each, alternated window by window: a captured
+    ``rows``-row decode step and one eager ``prefill``-token prefill forward."""
+    from llm_sharding_amd.config import get_preset
+    from llm_sharding_amd.runtime.engine import DecodeGraph, RandomSource
+    from llm_sharding_amd.runtime.engine_int4 import make_stage_engine
+    cfg = get_preset(model)
+    graphs, engines = {}, {}
+    for flag in ("1", "0"):  # the switch is read when the engine allocates and when the graph is captured
+        os.environ["LSA_MX4_GEMM"] = flag
+        e = make_stage_engine(cfg, 0, layers, DEV, torch.bfloat16, has_embed=True, has_head=True, source=RandomSource(cfg, 0),
+                              max_slots=rows, max_seq=max(256, prefill), max_prefill_rows=max(rows, prefill),
+                              weight_dtype="mxfp4")
+        for s in range(rows):
+            e.seq_len[s] = 128
+        graphs[flag], engines[flag] = DecodeGraph(e, rows, "full", slots=list(range(rows))).capture(), e
+    toks = torch.randint(3, cfg.vocab_size - 1, (prefill,), device=DEV)
+
+    def run_step(flag):
+        g = graphs[flag]
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        g.set_positions()
+        g.replay()
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(n_steps):
+            g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n_steps
+
+    def run_prefill(flag):
+        e = engines[flag]
+        os.environ["LSA_MX4_GEMM"] = flag
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e.seq_len[0] = 0
+        sl, po = e.prefill_rows([0], [prefill])
+        h = e.embed(toks)
+        torch.cuda.synchronize()
+        a.record()
+        e.forward(h, sl, po)
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    for table, fn in (("gemm_step", run_step), ("gemm_prefill", run_prefill)):
+        t = {f: [] for f in graphs}
+        for _ in range(windows + 1):  # the first window warms up
+            for f in graphs:
+                t[f].append(fn(f))
+        line = {"table": table, "model": model, "layers": layers, "rows": rows if table == "gemm_step" else prefill,
+                "windows": windows}
+        for f, name in (("1", "native"), ("0", "dequant")):
+            v = t[f][1:]
+            line[name + "_ms"] = round(statistics.median(v), 4)
+            line[name + "_spread"] = round((max(v) - min(v)) / statistics.median(v), 3)
+        print(json.dumps(line), flush=True)
+        out.append(line)
+    del os.environ["LSA_MX4_GEMM"]
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--steps", action="store_true")
+    ap.add_argument("--gemm", action="store_true", help="the W4A8 GEMM's table (256..2048 rows)")
+    ap.add_argument("--gemm-step", action="store_true", help="a 512-row decode step and a 2048-token prefill, LSA_MX4_GEMM=1 / 0")
+    ap.add_argument("--gemm-rows", default="256,512,1024,2048")
     ap.add_argument("--model", default="llama2-7b")
     ap.add_argument("--layers", type=int, default=0, help="--steps: only the first N layers (0: all)")
     ap.add_argument("--rows", default="1,16,32,64,128")
@@ -150,6 +260,10 @@ def main() -> None:
         kernels(a.model, [int(r) for r in a.rows.split(",")], a.windows, out)
     if a.steps:
         steps(a.model, [int(b) for b in a.batches.split(",")], a.windows, a.n_steps, a.layers, out)
+    if a.gemm:
+        gemm(a.model, [int(r) for r in a.gemm_rows.split(",")], a.windows, out)
+    if a.gemm_step:
+        gemm_step(a.model, a.layers or 4, 512, 2048, a.windows, a.n_steps, out)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
