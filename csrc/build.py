@@ -58,7 +58,9 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     # csrc/sampling/: the sampling kernels, outside the greedy path's recorded numerics inputs
     # csrc/cache/: KV-cache management (fork), outside them too
     # csrc/spec/: speculative decoding's draft / accept kernels, outside them too
-    # csrc/quant/: the int4 weight format's decode GEMV, which the bf16 greedy path never launches
+    # csrc/quant/: the 4-bit weight formats' projections, which the bf16 greedy path never launches -
+    # int4 (W4A16: GEMV, cooperative GEMV, GEMM) and mxfp4 (W4A8: GEMV, activation pre-pass, GEMM);
+    # their shared tails (split-K hand-off, epilogues, host checks) are the w4_*.h headers there
     # csrc/gemm_skp/: gemm_sk's split-K projections with the fix-up shared by all contributors
     # (includes kernels/gemm_sk.hip unchanged; the engine routes to it in runtime/engine_skp.py)
     kernel_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) +

@@ -35,68 +35,28 @@
 //    256 registers, 54 VGPRs spilled to 148 bytes of scratch per lane - a kernel that spills is not
 //    done, so ONLY BN 128 IS BUILT; the body stays a template on FN.
 //  * K is split over SK workgroups in whole groups (SK in 1 / 2 / 4 / 8, SK <= K / 128) where
-//    ceil(M / 128) * N / BN tiles do not fill the CUs, with gemv_coop_int4.hip's wait-free hand-off:
-//    fp32 partial tiles, fragment-native, stored to the slab with write-through (sc1) 16-B stores,
-//    one arrival counter per output tile; the last arriver sums the splits in fixed split order,
-//    resets the counter (replay-safe in a hipGraph) and runs the epilogue. No workgroup waits.
+//    ceil(M / 128) * N / BN tiles do not fill the CUs, with the wait-free hand-off of w4_common.h,
+//    one arrival counter per output tile (w4_gemm_tail.h, shared with gemm_mx4.hip).
 //  * epilogues: EPI_STORE (bias, GELU), EPI_RESID (bias; ss_out), EPI_SWIGLU (ss_in), EPI_QKV (RoPE
-//    or bias, KV append; ss_in), through epilogue.h's row16 helpers; the fused-RMSNorm fields as in
-//    gemm_sk.hip (ss_out: per-64-column sums of squares of the rounded outputs, (s0 + s1) + (s2 + s3)).
-#include "../kernels/epilogue.h"
-
-#include <utility>
+//    or bias, KV append; ss_in), with the fused-RMSNorm fields: w4_gemm_tail.h.
+#include "w4_gemm_tail.h"
 
 namespace {
 
-constexpr unsigned kNibMask = 0x00780078u;  // a nibble at mantissa bits 3..6 of both halves
-constexpr unsigned kBf16x16 = 0x41804180u;  // bf16 (16.0, 16.0)
-constexpr unsigned kBf16One = 0x3f803f80u;  // bf16 (1.0, 1.0)
-constexpr float kOffset = 24.0f;            // 16 (the bf16 base) + 8 (the nibble offset)
-
-constexpr int GI_BM = 128, GI_NTHR = 256, GI_NS = 4;
+constexpr int GI_BM = W4TileGeo<1>::BM, GI_NS = 4;
 constexpr int GI_HALF = GI_BM * 128;  // one 64-k image of 128-byte rows: 16 KiB
 constexpr int GI_ABUF = 2 * GI_HALF;  // one 128-k group of A: 32 KiB
 
-// one packed dword (8 nibbles) -> 8 bf16 (q + 24); mask / base arrive as registers so that
-// (w & mask) | base is one v_and_or_b32 (gemv_int4.hip)
-LSA_DEVICE u32x4_t int4x8_to_bf16(unsigned w, unsigned mask, unsigned base) {
-  u32x4_t r;
-  r[0] = (w & mask) | base;
-  r[1] = (__builtin_amdgcn_alignbit(w, w, 4) & mask) | base;
-  r[2] = (__builtin_amdgcn_alignbit(w, w, 8) & mask) | base;
-  r[3] = (__builtin_amdgcn_alignbit(w, w, 12) & mask) | base;
-  return r;
-}
-
-template <int N>
-LSA_DEVICE void gi_vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-template <int... S, typename F>
-LSA_DEVICE void gi_static_for(std::integer_sequence<int, S...>, F&& f) {
-  (f(std::integral_constant<int, S>{}), ...);
-}
-
-LSA_DEVICE void gi_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int FN>
-struct GiGeo {
-  static constexpr int TN = FN * 16, BN = 4 * TN, TILES = 4 * FN;
+struct GiGeo : W4TileGeo<FN> {
+  using W4TileGeo<FN>::EPI_BYTES;
   static constexpr int ADMA = GI_ABUF / 1024 / 4;  // A DMA instructions per wave and group (8)
   static constexpr int PER = ADMA + 2 * FN;        // VMEM instructions per wave and group
-  static constexpr int ELD = TN + 4;               // fp32 row stride of a wave's epilogue image
-  static constexpr int EPI_BYTES = 4 * GI_BM * ELD * 4;
   static constexpr int RING = GI_NS * GI_ABUF;
   static constexpr int RS_OFF = RING > EPI_BYTES ? RING : EPI_BYTES;  // row sums [2][128] fp32
   static constexpr int RSTD_OFF = RS_OFF + 2 * GI_BM * 4;             // row rstd [128] fp32
   static constexpr int FLAG_OFF = RSTD_OFF + GI_BM * 4;
   static constexpr int SMEM = FLAG_OFF + 16;
-  static constexpr int TILE_F4 = 4 * 8 * FN * 64;  // f32x4 fragments of one partial tile
   static_assert(SMEM <= 160 * 1024, "LDS budget");
   static_assert(ADMA == 8, "one A DMA per MFMA phase");
   static_assert(PER <= 63, "vmcnt range");
@@ -116,7 +76,7 @@ LSA_DEVICE void gemm_int4_body(unsigned char* smem, const bf16_raw* __restrict__
                                int K, int SK, const EpiArgs& ep, float* __restrict__ slab,
                                unsigned* __restrict__ counters) {
   using Geo = GiGeo<FN>;
-  constexpr int TN = Geo::TN, BN = Geo::BN, NS = GI_NS, TILES = Geo::TILES, ELD = Geo::ELD;
+  constexpr int TN = Geo::TN, BN = Geo::BN, NS = GI_NS;
   const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // column owner
   const int G = K >> 7, MT = (M + GI_BM - 1) / GI_BM, NT = N / BN, NTILES = MT * NT;
@@ -201,22 +161,22 @@ LSA_DEVICE void gemm_int4_body(unsigned char* smem, const bf16_raw* __restrict__
   };
 
   // prologue: groups 0 .. NS-2 in flight (per group: W then A)
-  gi_static_for(std::make_integer_sequence<int, NS - 1>{}, [&](auto sc) {
+  static_for(std::make_integer_sequence<int, NS - 1>{}, [&](auto sc) {
     constexpr int S = decltype(sc)::value;
     load_b(min(S, last), bw[S], sw[S]);
 #pragma unroll
     for (int d = 0; d < Geo::ADMA; ++d) dma(S, d, min(S, last));
   });
-  gi_vm_wait<Geo::PER>();
-  gi_barrier();
+  vm_wait<Geo::PER>();
+  fenced_barrier();
 #pragma unroll
   for (int i = 0; i < 4; ++i) af[0][i] = rd(0, 0, i);
   row_sums(0, 0);
 
   auto step = [&](int c, auto slot_c) {
     constexpr int slot = decltype(slot_c)::value, nslot = (slot + NS - 1) % NS, s1 = (slot + 1) % NS;
-    gi_vm_wait<Geo::PER>();
-    gi_barrier();
+    vm_wait<Geo::PER>();
+    fenced_barrier();
     const int cp = min(c + NS - 1, last);  // past the end: re-fetch the last group (dead)
     load_b(cp, bw[nslot], sw[nslot]);
     u32x4_t bf[4][FN];
@@ -259,191 +219,30 @@ LSA_DEVICE void gemm_int4_body(unsigned char* smem, const bf16_raw* __restrict__
     }
   };
   for (int c = 0; c < nchunk; c += NS) {
-    gi_static_for(std::make_integer_sequence<int, NS>{}, [&](auto sc) {
+    static_for(std::make_integer_sequence<int, NS>{}, [&](auto sc) {
       if (c + decltype(sc)::value < nchunk) step(c + decltype(sc)::value, sc);
     });
   }
-  gi_vm_wait<0>();  // the dead prefetches land before the LDS is reused ...
+  vm_wait<0>();  // the dead prefetches land before the LDS is reused ...
   // ... and before their destination registers are (gemm_wr.hip): keep the ring live up to here
 #pragma unroll
   for (int sl = 0; sl < NS; ++sl)
 #pragma unroll
     for (int j = 0; j < FN; ++j) asm volatile("" ::"v"(bw[sl][j]), "v"(sw[sl][j]));
-  gi_barrier();
+  fenced_barrier();
 
-  const int tid0 = tid == 0;
-  if (SK > 1) {
-    // Split-K hand-off as in gemv_coop_int4.hip: partials stored write-through (sc1, 16-B stores),
-    // every wave drains its stores, the workgroup barriers, one lane takes a relaxed agent-scope
-    // ticket; the workgroup that draws SK-1 reads all splits with sc1 loads in split order.
-    // Slab: [SK][tile][wave][row block][j][lane] f32x4 (fragment-native).
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)slab, (short)0, 0x7fffffff, 0x00020000);
-    const int split_stride = NTILES * Geo::TILE_F4 * 16;  // bytes (host: SK * split_stride < 2^31)
-    const int frag0 = ((tile * 4 + w) * 8 * FN * 64 + lane) * 16;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[i][j]), pr, frag0 + (i * FN + j) * 1024,
-                                               s * split_stride, 16 /* sc1 */);
-    gi_vm_wait<0>();
-    __syncthreads();
-    if (tid0) {
-      const unsigned old = __hip_atomic_fetch_add(&counters[tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = old == (unsigned)(SK - 1);
-    }
-    __syncthreads();
-    if (!*s_flag) return;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = fzero;
-    for (int q = 0; q < SK; ++q) {
-      f32x4_t v[8][FN];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          v[i][j] = __builtin_bit_cast(
-              f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(pr, frag0 + (i * FN + j) * 1024, q * split_stride, 16));
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] += v[i][j][r];  // element by element: no packed FP32 adds
-    }
-    if (tid0) __hip_atomic_store(&counters[tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-
-  // epilogue: the fp32 tile through per-wave LDS images; one thread per (row, 16 columns) unit,
-  // the TILES units of a row in consecutive threads, runs the row16 epilogues of epilogue.h. With
-  // ss_in, the fused RMSNorm's row scale first, summed in gemm_sk's order.
-  constexpr bool NORM_IN = EPI == EPI_QKV || EPI == EPI_SWIGLU;
-  if (NORM_IN && ep.ss_in) {
-    for (int r = tid; r < GI_BM; r += GI_NTHR) {
-      const float* sp = ep.ss_in + (size_t)min(m0 + r, M - 1) * ep.ss_n;
-      float tsum = 0.f;
-      for (int i0 = 0; i0 < ep.ss_n; i0 += 4) {
-        const f32x4_t q4 = *reinterpret_cast<const f32x4_t*>(sp + i0);
-        tsum += (q4[0] + q4[1]) + (q4[2] + q4[3]);
-      }
-      s_rstd[r] = rsqrtf(tsum / (float)(64 * ep.ss_n) + ep.ss_eps);
-    }
-  }
-  float* img = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        img[w * (GI_BM * ELD) + (i * 16 + 4 * kq + r) * ELD + j * 16 + (lane & 15)] = acc[i][j][r];
-  __syncthreads();
-  auto unit = [&](int row, int jt, float* v) {  // 16-column tile jt of the workgroup's BN columns
-    const float* src = img + (jt / FN) * (GI_BM * ELD) + row * ELD + (jt % FN) * 16;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4_t*>(v + 4 * q) = *reinterpret_cast<const f32x4_t*>(src + 4 * q);
-  };
-  const int col0 = nt * BN;
-  if constexpr (EPI == EPI_SWIGLU) {
-    // 16-column tiles interleave gate / up (packing.fuse_gate_up): pair jp of the workgroup
-    // writes output columns col0 / 2 + 16 jp
-    constexpr int PAIRS = TILES / 2;
-#pragma unroll
-    for (int s2 = 0; s2 < (GI_BM * PAIRS) / GI_NTHR; ++s2) {
-      const int u = tid + GI_NTHR * s2, row = u / PAIRS, jp = u % PAIRS;
-      const int m = m0 + row;
-      float g[16], up[16];
-      unit(row, 2 * jp, g);
-      unit(row, 2 * jp + 1, up);
-      if (m < M) {
-        const float rsc = ep.ss_in ? s_rstd[row] : 1.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) g[q] = silu(g[q] * rsc) * (up[q] * rsc);
-        bf16_raw* o = ep.out + (size_t)m * ep.ldo + col0 / 2 + jp * 16;
-        st16(o, pack8(g));
-        st16(o + 8, pack8(g + 8));
-      }
-    }
-  } else {
-#pragma unroll
-    for (int s2 = 0; s2 < (GI_BM * TILES) / GI_NTHR; ++s2) {
-      const int u = tid + GI_NTHR * s2, row = u / TILES, jt = u % TILES;
-      const int m = m0 + row, c0 = col0 + jt * 16;
-      float v[16];
-      unit(row, jt, v);
-      if (EPI == EPI_RESID && ep.ss_out) {
-        // residual add + the row's sum of squares of the ROUNDED outputs over the 64 columns of
-        // 4 consecutive threads (gemm_sk.hip)
-        float ssq = 0.f;
-        if (m < M) {
-          epi_bias16(ep, c0, v);
-          const bf16_raw* rr = ep.resid + (size_t)m * ep.ldr + c0;
-          float x0[8], x1[8];
-          unpack8(ld16(rr), x0);
-          unpack8(ld16(rr + 8), x1);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            x0[q] += v[q];
-            x1[q] += v[q + 8];
-          }
-          const u32x4_t p0 = pack8(x0), p1 = pack8(x1);
-          bf16_raw* o = ep.out + (size_t)m * ep.ldo + c0;
-          st16(o, p0);
-          st16(o + 8, p1);
-          unpack8(p0, x0);
-          unpack8(p1, x1);
-          ssq = ss16(x0, x1);
-        }
-        // (s0 + s1) + (s2 + s3) over the 4 units of the 64-column block (lsa_row_ss order)
-#pragma unroll
-        for (int o = 1; o < 4; o <<= 1) ssq = __fadd_rn(ssq, __shfl_xor(ssq, o, 64));
-        if (m < M && (jt & 3) == 0) ep.ss_out[(size_t)m * ep.ss_n + (c0 >> 6)] = ssq;
-      } else if (m < M) {
-        if (EPI == EPI_QKV && ep.ss_in) {
-          const float rsc = s_rstd[row];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) v[q] *= rsc;
-        }
-        epi_row16<EPI>(ep, m, c0, v);
-      }
-    }
-  }
+  // the split-K hand-off and the epilogue: w4_gemm_tail.h
+  if (SK > 1 && !w4_gemm_splitk<FN>(acc, slab, counters, s_flag, tile, NTILES, s, SK)) return;
+  w4_gemm_epilogue<FN, EPI>(smem, s_rstd, acc, ep, M, m0, nt * BN);
 }
 
 template <int FN, int EPI>
-__global__ __launch_bounds__(GI_NTHR) void gemm_int4_kernel(const bf16_raw* __restrict__ A, int lda,
-                                                            const unsigned char* __restrict__ wq,
-                                                            const float* __restrict__ wscale, int M, int N, int K,
-                                                            int SK, EpiArgs ep, float* __restrict__ slab,
-                                                            unsigned* __restrict__ counters) {
+__global__ __launch_bounds__(GiGeo<FN>::NTHR) void gemm_int4_kernel(
+    const bf16_raw* __restrict__ A, int lda, const unsigned char* __restrict__ wq, const float* __restrict__ wscale,
+    int M, int N, int K, int SK, EpiArgs ep, float* __restrict__ slab, unsigned* __restrict__ counters) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[GiGeo<FN>::SMEM];
   gemm_int4_body<FN, EPI>(smem, A, lda, wq, wscale, M, N, K, SK, ep, slab, counters);
 }
-
-template <int FN, int EPI>
-int gi_launch(const bf16_raw* A, int lda, const unsigned char* wq, const float* ws, int M, int N, int K, int SK,
-              const EpiArgs& ep, float* slab, unsigned* cnt, hipStream_t s) {
-  const int tiles = ((M + GI_BM - 1) / GI_BM) * (N / GiGeo<FN>::BN);
-  gemm_int4_kernel<FN, EPI><<<tiles * SK, GI_NTHR, 0, s>>>(A, lda, wq, ws, M, N, K, SK, ep, slab, cnt);
-  LSA_CHECK_LAUNCH();
-  return LSA_OK;
-}
-
-template <int FN>
-int gi_launch_epi(int epi, const bf16_raw* A, int lda, const unsigned char* wq, const float* ws, int M, int N, int K,
-                  int SK, const EpiArgs& ep, float* slab, unsigned* cnt, hipStream_t s) {
-  switch (epi) {
-    case EPI_STORE: return gi_launch<FN, EPI_STORE>(A, lda, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_RESID: return gi_launch<FN, EPI_RESID>(A, lda, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_SWIGLU: return gi_launch<FN, EPI_SWIGLU>(A, lda, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_QKV: return gi_launch<FN, EPI_QKV>(A, lda, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    default: return LSA_UNSUPPORTED;
-  }
-}
-
-bool gi_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -455,38 +254,20 @@ bool gi_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 
 extern "C" int lsa_gemm_int4(const void* a, int lda, const void* wq4, const float* scales, int M, int N, int K, int epi,
                              const EpiArgs* ep, int bn, int depth, int sk, float* slab, long long slab_floats,
                              unsigned* counters, int n_counters, hipStream_t stream) {
-  if (!a || !wq4 || !scales || !ep || M < 1 || N < 1 || K < 128 || K % 128 || lda < K || lda % 8 || !gi_aligned16(a))
+  if (!a || !wq4 || !scales || !ep || M < 1 || N < 1 || K < 128 || K % 128 || lda < K || lda % 8 || !aligned16(a))
     return LSA_BAD_SHAPE;
   if (bn != 128 || depth != GI_NS) return LSA_UNSUPPORTED;
-  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU && epi != EPI_QKV) return LSA_UNSUPPORTED;
-  if (N % bn) return LSA_BAD_SHAPE;
-  if ((sk != 1 && sk != 2 && sk != 4 && sk != 8) || sk > K / 128) return LSA_BAD_SHAPE;
-  const long long mt = (M + GI_BM - 1) / GI_BM, tiles = mt * (N / bn);
-  if (tiles * sk > 0x7fffffffLL || (long long)M * lda > 0x3fffffffLL) return LSA_BAD_SHAPE;
-  if (sk > 1) {
-    const long long need = (long long)sk * mt * GI_BM * N;
-    if (!slab || !counters || slab_floats < need || need * 4 > 0x7fffffffLL || n_counters < tiles || !gi_aligned16(slab))
+  return dispatch_epi(epi, [&](auto e) -> int {  // an unknown epilogue is refused before the checks below
+    constexpr int FN = 2, EPI = decltype(e)::value;
+    if (N % bn || (long long)M * lda > 0x3fffffffLL) return LSA_BAD_SHAPE;
+    if (check_gemm_split(sk, K / 128, M, N, bn, slab, slab_floats, counters, n_counters) != LSA_OK ||
+        check_epi_args(epi, ep, N, K) != LSA_OK)
       return LSA_BAD_SHAPE;
-  }
-  // the row16 epilogues store and load 16-B runs
-  if (!ep->out || !gi_aligned16(ep->out) || !gi_aligned16(ep->bias) || ep->ldo % 8) return LSA_BAD_SHAPE;
-  if (epi == EPI_STORE && ep->ldo < N) return LSA_BAD_SHAPE;
-  if (epi == EPI_RESID && (!ep->resid || !gi_aligned16(ep->resid) || ep->ldo < N || ep->ldr < N || ep->ldr % 8))
-    return LSA_BAD_SHAPE;
-  if (epi == EPI_SWIGLU && (ep->ldo < N / 2 || ep->act || ep->bias)) return LSA_BAD_SHAPE;
-  if (epi == EPI_QKV) {
-    const int hd = ep->head_dim;
-    if (!ep->k_cache || !ep->v_cache || !ep->slot || !ep->pos || hd < 16 || (hd & (hd - 1)) ||
-        N != (ep->n_heads + 2 * ep->n_kv) * hd || !gi_aligned16(ep->k_cache) || !gi_aligned16(ep->v_cache) ||
-        !gi_aligned16(ep->cos_t) || !gi_aligned16(ep->sin_t) || (ep->cos_t == nullptr) != (ep->sin_t == nullptr))
-      return LSA_BAD_SHAPE;
-  }
-  if (epi != EPI_STORE && ep->act) return LSA_BAD_SHAPE;
-  if (ep->ss_out && (epi != EPI_RESID || N % 64 || ep->ss_n != N / 64)) return LSA_BAD_SHAPE;
-  if (ep->ss_in && ((epi != EPI_QKV && epi != EPI_SWIGLU) || ep->ss_n < 4 || ep->ss_n % 4 || K != 64 * ep->ss_n ||
-                    !gi_aligned16(ep->ss_in)))
-    return LSA_BAD_SHAPE;
-  const bf16_raw* A = static_cast<const bf16_raw*>(a);
-  const unsigned char* w = static_cast<const unsigned char*>(wq4);
-  return gi_launch_epi<2>(epi, A, lda, w, scales, M, N, K, sk, *ep, slab, counters, stream);
+    const int tiles = ((M + GiGeo<FN>::BM - 1) / GiGeo<FN>::BM) * (N / GiGeo<FN>::BN);
+    gemm_int4_kernel<FN, EPI><<<tiles * sk, GiGeo<FN>::NTHR, 0, stream>>>(
+        static_cast<const bf16_raw*>(a), lda, static_cast<const unsigned char*>(wq4), scales, M, N, K, sk, *ep, slab,
+        counters);
+    LSA_CHECK_LAUNCH();
+    return LSA_OK;
+  });
 }

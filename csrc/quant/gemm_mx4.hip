@@ -29,26 +29,22 @@
 //    FN MFMAs of K = 128 and 16 ds_read_b128, with no branch in the step so that the reads run
 //    ahead of the MFMAs. Row blocks past ceil(M/16) re-read the last one and are masked at the store.
 //  * K is split over SK workgroups in whole 512-k scale groups (the last may be short) where the
-//    output tiles do not fill the CUs, with gemv_coop_int4.hip's wait-free hand-off as
-//    gemm_int4.hip has it: fragment-native fp32 partial tiles stored write-through (sc1), one
-//    arrival counter per output tile, the last arriver sums the splits in fixed order, resets the
-//    counter (replay-safe in a captured graph) and runs the epilogue. No workgroup waits.
-//  * epilogues and the fused-RMSNorm fields: gemm_int4.hip's, through epilogue.h's row16 helpers.
+//    output tiles do not fill the CUs, with the wait-free hand-off of w4_common.h, one arrival
+//    counter per output tile (w4_gemm_tail.h, shared with gemm_int4.hip).
+//  * epilogues and the fused-RMSNorm fields: w4_gemm_tail.h.
 //  * registers, hipcc's report (-Rpass-analysis=kernel-resource-usage): BN 128 (FN 2): 146-147
 //    VGPRs + 64 AGPRs, 74256 B of LDS, no scratch, for all four epilogues. BN 256 (FN 4): 254 VGPRs +
 //    128 AGPRs, 139792 B of LDS, no scratch for STORE / RESID but 36 bytes of scratch per lane for
 //    SWIGLU / QKV - a kernel that spills is not done, so ONLY BN 128 IS BUILT; the body stays a
 //    template on FN.
-#include "../kernels/epilogue.h"
 #include "mx8_quant.h"
-
-#include <utility>
+#include "w4_gemm_tail.h"
 
 namespace {
 
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
-constexpr int GM_BM = 128, GM_NTHR = 256, GM_NS = 4;
+constexpr int GM_BM = W4TileGeo<1>::BM, GM_NS = 4;
 constexpr int GM_ASTEP = GM_BM * 128;  // e4m3 codes of one K-step of a row tile: 16 KiB
 constexpr int GM_ADMA = GM_ASTEP / 1024 / 4;  // A DMA instructions per wave and K-step (4)
 
@@ -82,34 +78,15 @@ __global__ __launch_bounds__(256) void quant_act_mx8_kernel(const bf16_raw* __re
 }
 
 // ------------------------------------------------------------------------------ the GEMM
-template <int N>
-LSA_DEVICE void gm_vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-template <int... S, typename F>
-LSA_DEVICE void gm_static_for(std::integer_sequence<int, S...>, F&& f) {
-  (f(std::integral_constant<int, S>{}), ...);
-}
-
-LSA_DEVICE void gm_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int FN>
-struct GmGeo {
-  static constexpr int TN = FN * 16, BN = 4 * TN, TILES = 4 * FN;
+struct GmGeo : W4TileGeo<FN> {
+  using W4TileGeo<FN>::EPI_BYTES;
   static constexpr int PER = FN + GM_ADMA;  // VMEM instructions per wave and K-step
   static constexpr int GRP = FN + 8;        // + per 512-k group: FN weight scale dwords, 8 A exponent dwords
-  static constexpr int ELD = TN + 4;        // fp32 row stride of a wave's epilogue image
-  static constexpr int EPI_BYTES = 4 * GM_BM * ELD * 4;
   static constexpr int RING = GM_NS * GM_ASTEP;
   static constexpr int RSTD_OFF = RING > EPI_BYTES ? RING : EPI_BYTES;  // row rstd [128] fp32
   static constexpr int FLAG_OFF = RSTD_OFF + GM_BM * 4;
   static constexpr int SMEM = FLAG_OFF + 16;
-  static constexpr int TILE_F4 = 4 * 8 * FN * 64;  // f32x4 fragments of one partial tile
   static_assert(SMEM <= 160 * 1024, "LDS budget");
   static_assert(GM_ADMA == 4, "one A DMA per pair of row blocks' MFMAs");
   static_assert(2 * PER + GRP <= 63, "vmcnt range");
@@ -127,8 +104,8 @@ LSA_DEVICE void gemm_mx4_body(unsigned char* smem, const unsigned char* __restri
                               const unsigned* __restrict__ wscale, int M, int N, int K, int SK, const EpiArgs& ep,
                               float* __restrict__ slab, unsigned* __restrict__ counters) {
   using Geo = GmGeo<FN>;
-  constexpr int TN = Geo::TN, BN = Geo::BN, NS = GM_NS, TILES = Geo::TILES, ELD = Geo::ELD;
-  const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
+  constexpr int TN = Geo::TN, BN = Geo::BN, NS = GM_NS;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // column owner
   const int KS = K >> 7, NG = (KS + 3) >> 2, RB = (M + 15) >> 4;
   const int MT = (M + GM_BM - 1) / GM_BM, NT = N / BN, NTILES = MT * NT;
@@ -193,7 +170,7 @@ LSA_DEVICE void gemm_mx4_body(unsigned char* smem, const unsigned char* __restri
 
   // prologue: the first group's dwords, then steps 0 .. 2 (per step: W then A)
   load_grp(0, sc, ex);
-  gm_static_for(std::make_integer_sequence<int, NS - 1>{}, [&](auto sl) {
+  static_for(std::make_integer_sequence<int, NS - 1>{}, [&](auto sl) {
     constexpr int S = decltype(sl)::value;
     load_b(min(S, last), bw[S]);
 #pragma unroll
@@ -202,8 +179,8 @@ LSA_DEVICE void gemm_mx4_body(unsigned char* smem, const unsigned char* __restri
 
   auto step = [&](int c, auto slot_c) {
     constexpr int S = decltype(slot_c)::value, nslot = (S + NS - 1) % NS;
-    gm_vm_wait<2 * Geo::PER + ((S == 1 || S == 2) ? Geo::GRP : 0)>();
-    gm_barrier();
+    vm_wait<2 * Geo::PER + ((S == 1 || S == 2) ? Geo::GRP : 0)>();
+    fenced_barrier();
     const int cp = min(c + NS - 1, last);  // past the end: re-fetch the last step (dead)
     load_b(cp, bw[nslot]);
     if (S == 0) load_grp(min((c >> 2) + 1, glast), scn, exn);
@@ -232,11 +209,11 @@ LSA_DEVICE void gemm_mx4_body(unsigned char* smem, const unsigned char* __restri
     }
   };
   for (int c = 0; c < nstep; c += NS) {
-    gm_static_for(std::make_integer_sequence<int, NS>{}, [&](auto sl) {
+    static_for(std::make_integer_sequence<int, NS>{}, [&](auto sl) {
       if (c + decltype(sl)::value < nstep) step(c + decltype(sl)::value, sl);
     });
   }
-  gm_vm_wait<0>();  // the dead prefetches land before the LDS is reused ...
+  vm_wait<0>();  // the dead prefetches land before the LDS is reused ...
   // ... and before their destination registers are (gemm_wr.hip): keep the rings live up to here
 #pragma unroll
   for (int sl = 0; sl < NS; ++sl)
@@ -246,181 +223,21 @@ LSA_DEVICE void gemm_mx4_body(unsigned char* smem, const unsigned char* __restri
   for (int j = 0; j < FN; ++j) asm volatile("" ::"v"(sc[j]), "v"(scn[j]));
 #pragma unroll
   for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(ex[i]), "v"(exn[i]));
-  gm_barrier();
+  fenced_barrier();
 
-  const int tid0 = tid == 0;
-  if (SK > 1) {
-    // Split-K hand-off as in gemm_int4.hip: partials stored write-through (sc1, 16-B stores),
-    // every wave drains its stores, the workgroup barriers, one lane takes a relaxed agent-scope
-    // ticket; the workgroup that draws SK-1 reads all splits with sc1 loads in split order.
-    // Slab: [SK][tile][wave][row block][j][lane] f32x4 (fragment-native).
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)slab, (short)0, 0x7fffffff, 0x00020000);
-    const int split_stride = NTILES * Geo::TILE_F4 * 16;  // bytes (host: SK * split_stride < 2^31)
-    const int frag0 = ((tile * 4 + w) * 8 * FN * 64 + lane) * 16;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[i][j]), pr, frag0 + (i * FN + j) * 1024,
-                                               s * split_stride, 16 /* sc1 */);
-    gm_vm_wait<0>();
-    __syncthreads();
-    if (tid0) {
-      const unsigned old = __hip_atomic_fetch_add(&counters[tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *s_flag = old == (unsigned)(SK - 1);
-    }
-    __syncthreads();
-    if (!*s_flag) return;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = fzero;
-    for (int q = 0; q < SK; ++q) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        f32x4_t v[FN];
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          v[j] = __builtin_bit_cast(
-              f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(pr, frag0 + (i * FN + j) * 1024, q * split_stride, 16));
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] += v[j][r];  // element by element: no packed FP32 adds
-      }
-    }
-    if (tid0) __hip_atomic_store(&counters[tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-
-  // epilogue (gemm_int4.hip's): the fp32 tile through per-wave LDS images; one thread per (row,
-  // 16 columns) unit, the TILES units of a row in consecutive threads, runs the row16 epilogues of
-  // epilogue.h. With ss_in, the fused RMSNorm's row scale first, summed in gemm_sk's order.
-  constexpr bool NORM_IN = EPI == EPI_QKV || EPI == EPI_SWIGLU;
-  if (NORM_IN && ep.ss_in) {
-    for (int r = tid; r < GM_BM; r += GM_NTHR) {
-      const float* sp = ep.ss_in + (size_t)min(m0 + r, M - 1) * ep.ss_n;
-      float tsum = 0.f;
-      for (int i0 = 0; i0 < ep.ss_n; i0 += 4) {
-        const f32x4_t q4 = *reinterpret_cast<const f32x4_t*>(sp + i0);
-        tsum += (q4[0] + q4[1]) + (q4[2] + q4[3]);
-      }
-      s_rstd[r] = rsqrtf(tsum / (float)(64 * ep.ss_n) + ep.ss_eps);
-    }
-  }
-  float* img = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        img[w * (GM_BM * ELD) + (i * 16 + 4 * kq + r) * ELD + j * 16 + (lane & 15)] = acc[i][j][r];
-  __syncthreads();
-  auto unit = [&](int row, int jt, float* v) {  // 16-column tile jt of the workgroup's BN columns
-    const float* src = img + (jt / FN) * (GM_BM * ELD) + row * ELD + (jt % FN) * 16;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4_t*>(v + 4 * q) = *reinterpret_cast<const f32x4_t*>(src + 4 * q);
-  };
-  const int col0 = nt * BN;
-  if constexpr (EPI == EPI_SWIGLU) {
-    // 16-column tiles interleave gate / up (packing.fuse_gate_up): pair jp of the workgroup
-    // writes output columns col0 / 2 + 16 jp
-    constexpr int PAIRS = TILES / 2;
-#pragma unroll
-    for (int s2 = 0; s2 < (GM_BM * PAIRS) / GM_NTHR; ++s2) {
-      const int u = tid + GM_NTHR * s2, row = u / PAIRS, jp = u % PAIRS;
-      const int m = m0 + row;
-      if (m < M) {
-        float g[16], up[16];
-        unit(row, 2 * jp, g);
-        unit(row, 2 * jp + 1, up);
-        const float rsc = ep.ss_in ? s_rstd[row] : 1.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) g[q] = silu(g[q] * rsc) * (up[q] * rsc);
-        bf16_raw* o = ep.out + (size_t)m * ep.ldo + col0 / 2 + jp * 16;
-        st16(o, pack8(g));
-        st16(o + 8, pack8(g + 8));
-      }
-    }
-  } else {
-#pragma unroll
-    for (int s2 = 0; s2 < (GM_BM * TILES) / GM_NTHR; ++s2) {
-      const int u = tid + GM_NTHR * s2, row = u / TILES, jt = u % TILES;
-      const int m = m0 + row, c0 = col0 + jt * 16;
-      float v[16];
-      unit(row, jt, v);
-      if (EPI == EPI_RESID && ep.ss_out) {
-        // residual add + the row's sum of squares of the ROUNDED outputs over the 64 columns of
-        // 4 consecutive threads (gemm_sk.hip)
-        float ssq = 0.f;
-        if (m < M) {
-          epi_bias16(ep, c0, v);
-          const bf16_raw* rr = ep.resid + (size_t)m * ep.ldr + c0;
-          float x0[8], x1[8];
-          unpack8(ld16(rr), x0);
-          unpack8(ld16(rr + 8), x1);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            x0[q] += v[q];
-            x1[q] += v[q + 8];
-          }
-          const u32x4_t p0 = pack8(x0), p1 = pack8(x1);
-          bf16_raw* o = ep.out + (size_t)m * ep.ldo + c0;
-          st16(o, p0);
-          st16(o + 8, p1);
-          unpack8(p0, x0);
-          unpack8(p1, x1);
-          ssq = ss16(x0, x1);
-        }
-        // (s0 + s1) + (s2 + s3) over the 4 units of the 64-column block (lsa_row_ss order)
-#pragma unroll
-        for (int o = 1; o < 4; o <<= 1) ssq = __fadd_rn(ssq, __shfl_xor(ssq, o, 64));
-        if (m < M && (jt & 3) == 0) ep.ss_out[(size_t)m * ep.ss_n + (c0 >> 6)] = ssq;
-      } else if (m < M) {
-        if (EPI == EPI_QKV && ep.ss_in) {
-          const float rsc = s_rstd[row];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) v[q] *= rsc;
-        }
-        epi_row16<EPI>(ep, m, c0, v);
-      }
-    }
-  }
+  // the split-K hand-off and the epilogue: w4_gemm_tail.h
+  if (SK > 1 && !w4_gemm_splitk<FN>(acc, slab, counters, s_flag, tile, NTILES, s, SK)) return;
+  w4_gemm_epilogue<FN, EPI>(smem, s_rstd, acc, ep, M, m0, nt * BN);
 }
 
 template <int FN, int EPI>
-__global__ __launch_bounds__(GM_NTHR) void gemm_mx4_kernel(const unsigned char* __restrict__ a8,
-                                                           const unsigned* __restrict__ ea,
-                                                           const unsigned char* __restrict__ wq,
-                                                           const unsigned* __restrict__ wscale, int M, int N, int K,
-                                                           int SK, EpiArgs ep, float* __restrict__ slab,
-                                                           unsigned* __restrict__ counters) {
+__global__ __launch_bounds__(GmGeo<FN>::NTHR) void gemm_mx4_kernel(
+    const unsigned char* __restrict__ a8, const unsigned* __restrict__ ea, const unsigned char* __restrict__ wq,
+    const unsigned* __restrict__ wscale, int M, int N, int K, int SK, EpiArgs ep, float* __restrict__ slab,
+    unsigned* __restrict__ counters) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[GmGeo<FN>::SMEM];
   gemm_mx4_body<FN, EPI>(smem, a8, ea, wq, wscale, M, N, K, SK, ep, slab, counters);
 }
-
-template <int FN, int EPI>
-int gm_launch(const unsigned char* a8, const unsigned* ea, const unsigned char* wq, const unsigned* ws, int M, int N,
-              int K, int SK, const EpiArgs& ep, float* slab, unsigned* cnt, hipStream_t s) {
-  const int tiles = ((M + GM_BM - 1) / GM_BM) * (N / GmGeo<FN>::BN);
-  gemm_mx4_kernel<FN, EPI><<<tiles * SK, GM_NTHR, 0, s>>>(a8, ea, wq, ws, M, N, K, SK, ep, slab, cnt);
-  LSA_CHECK_LAUNCH();
-  return LSA_OK;
-}
-
-template <int FN>
-int gm_launch_epi(int epi, const unsigned char* a8, const unsigned* ea, const unsigned char* wq, const unsigned* ws,
-                  int M, int N, int K, int SK, const EpiArgs& ep, float* slab, unsigned* cnt, hipStream_t s) {
-  switch (epi) {
-    case EPI_STORE: return gm_launch<FN, EPI_STORE>(a8, ea, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_RESID: return gm_launch<FN, EPI_RESID>(a8, ea, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_SWIGLU: return gm_launch<FN, EPI_SWIGLU>(a8, ea, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    case EPI_QKV: return gm_launch<FN, EPI_QKV>(a8, ea, wq, ws, M, N, K, SK, ep, slab, cnt, s);
-    default: return LSA_UNSUPPORTED;
-  }
-}
-
-bool gm_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -429,7 +246,7 @@ bool gm_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 
 // above). Every byte of both is written by every call.
 extern "C" int lsa_quant_act_mx8(const void* x, int ldx, const int* a_rows, void* a8, void* ea, int M, int K,
                                  hipStream_t stream) {
-  if (!x || !a8 || !ea || M < 1 || K < 128 || K % 128 || ldx < K || ldx % 8 || !gm_aligned16(x) || !gm_aligned16(a8) ||
+  if (!x || !a8 || !ea || M < 1 || K < 128 || K % 128 || ldx < K || ldx % 8 || !aligned16(x) || !aligned16(a8) ||
       (reinterpret_cast<size_t>(ea) & 3))
     return LSA_BAD_SHAPE;
   const long long RB = (M + 15) / 16, KS = K / 128, NG = (KS + 3) / 4;
@@ -449,41 +266,21 @@ extern "C" int lsa_quant_act_mx8(const void* x, int ldx, const int* a_rows, void
 extern "C" int lsa_gemm_mx4(const void* a8, const void* ea, const void* wq, const void* scales, int M, int N, int K,
                             int epi, const EpiArgs* ep, int bn, int sk, float* slab, long long slab_floats,
                             unsigned* counters, int n_counters, hipStream_t stream) {
-  if (!a8 || !ea || !wq || !scales || !ep || M < 1 || N < 1 || K < 128 || K % 128 || !gm_aligned16(a8) ||
-      !gm_aligned16(wq) || (reinterpret_cast<size_t>(ea) & 3) || (reinterpret_cast<size_t>(scales) & 3))
+  if (!a8 || !ea || !wq || !scales || !ep || M < 1 || N < 1 || K < 128 || K % 128 || !aligned16(a8) ||
+      !aligned16(wq) || (reinterpret_cast<size_t>(ea) & 3) || (reinterpret_cast<size_t>(scales) & 3))
     return LSA_BAD_SHAPE;
   if (bn != 128) return LSA_UNSUPPORTED;
-  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU && epi != EPI_QKV) return LSA_UNSUPPORTED;
-  if (N % bn || (long long)N * K / 2 >= (1ll << 31)) return LSA_BAD_SHAPE;
-  if ((sk != 1 && sk != 2 && sk != 4 && sk != 8) || sk > (K / 128 + 3) / 4) return LSA_BAD_SHAPE;
-  const long long mt = (M + GM_BM - 1) / GM_BM, tiles = mt * (N / bn);
-  if (tiles * sk > 0x7fffffffLL) return LSA_BAD_SHAPE;
-  if (sk > 1) {
-    const long long need = (long long)sk * mt * GM_BM * N;
-    if (!slab || !counters || slab_floats < need || need * 4 > 0x7fffffffLL || n_counters < tiles || !gm_aligned16(slab))
+  return dispatch_epi(epi, [&](auto e) -> int {  // an unknown epilogue is refused before the checks below
+    constexpr int FN = 2, EPI = decltype(e)::value;
+    if (N % bn || (long long)N * K / 2 >= (1ll << 31)) return LSA_BAD_SHAPE;
+    if (check_gemm_split(sk, (K / 128 + 3) / 4, M, N, bn, slab, slab_floats, counters, n_counters) != LSA_OK ||
+        check_epi_args(epi, ep, N, K) != LSA_OK)
       return LSA_BAD_SHAPE;
-  }
-  // the row16 epilogues store and load 16-B runs
-  if (!ep->out || !gm_aligned16(ep->out) || !gm_aligned16(ep->bias) || ep->ldo % 8) return LSA_BAD_SHAPE;
-  if (epi == EPI_STORE && ep->ldo < N) return LSA_BAD_SHAPE;
-  if (epi == EPI_RESID && (!ep->resid || !gm_aligned16(ep->resid) || ep->ldo < N || ep->ldr < N || ep->ldr % 8))
-    return LSA_BAD_SHAPE;
-  if (epi == EPI_SWIGLU && (ep->ldo < N / 2 || ep->act || ep->bias)) return LSA_BAD_SHAPE;
-  if (epi == EPI_QKV) {
-    const int hd = ep->head_dim;
-    if (!ep->k_cache || !ep->v_cache || !ep->slot || !ep->pos || hd < 16 || (hd & (hd - 1)) ||
-        N != (ep->n_heads + 2 * ep->n_kv) * hd || !gm_aligned16(ep->k_cache) || !gm_aligned16(ep->v_cache) ||
-        !gm_aligned16(ep->cos_t) || !gm_aligned16(ep->sin_t) || (ep->cos_t == nullptr) != (ep->sin_t == nullptr))
-      return LSA_BAD_SHAPE;
-  }
-  if (epi != EPI_STORE && ep->act) return LSA_BAD_SHAPE;
-  if (ep->ss_out && (epi != EPI_RESID || N % 64 || ep->ss_n != N / 64)) return LSA_BAD_SHAPE;
-  if (ep->ss_in && ((epi != EPI_QKV && epi != EPI_SWIGLU) || ep->ss_n < 4 || ep->ss_n % 4 || K != 64 * ep->ss_n ||
-                    !gm_aligned16(ep->ss_in)))
-    return LSA_BAD_SHAPE;
-  const unsigned char* a = static_cast<const unsigned char*>(a8);
-  const unsigned* e = static_cast<const unsigned*>(ea);
-  const unsigned char* w = static_cast<const unsigned char*>(wq);
-  const unsigned* sc = static_cast<const unsigned*>(scales);
-  return gm_launch_epi<2>(epi, a, e, w, sc, M, N, K, sk, *ep, slab, counters, stream);
+    const int tiles = ((M + GmGeo<FN>::BM - 1) / GmGeo<FN>::BM) * (N / GmGeo<FN>::BN);
+    gemm_mx4_kernel<FN, EPI><<<tiles * sk, GmGeo<FN>::NTHR, 0, stream>>>(
+        static_cast<const unsigned char*>(a8), static_cast<const unsigned*>(ea), static_cast<const unsigned char*>(wq),
+        static_cast<const unsigned*>(scales), M, N, K, sk, *ep, slab, counters);
+    LSA_CHECK_LAUNCH();
+    return LSA_OK;
+  });
 }

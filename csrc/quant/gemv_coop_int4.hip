@@ -19,36 +19,12 @@
 //    the fused RMSNorm's sum of squares is kept by the same threads. No MFMA is spent on either;
 //  * every wave streams only its own nibble loads (one 16-B load per tile and group) and their
 //    4-byte scales, non-temporal, D-1 chunks ahead in registers;
-//  * K is split over SK workgroups in whole groups; each stores fp32 partial tiles (and partial
-//    sums of squares) to a slab with write-through (sc1) stores, an arrival counter per column
-//    group decides the last arriver, which sums the splits in fixed order, resets the counter
-//    (replay-safe in a hipGraph) and runs the epilogue. No workgroup waits for another.
-#include "../kernels/epilogue.h"
-
-#include <utility>
+//  * K is split over SK workgroups in whole groups, with the wait-free hand-off of w4_common.h:
+//    fp32 partial tiles (and partial sums of squares) through a slab, an arrival counter per
+//    column group (w4_coop_tail.h, shared with gemv_mx4.hip).
+#include "w4_coop_tail.h"
 
 namespace {
-
-constexpr unsigned kNibMask = 0x00780078u;  // a nibble at mantissa bits 3..6 of both halves
-constexpr unsigned kBf16x16 = 0x41804180u;  // bf16 (16.0, 16.0)
-constexpr float kOffset = 24.0f;            // 16 (the bf16 base) + 8 (the nibble offset)
-
-// one packed dword (8 nibbles) -> 8 bf16 (q + 24); mask / base arrive as registers so that
-// (w & mask) | base is one v_and_or_b32 (gemv_int4.hip)
-LSA_DEVICE u32x4_t int4x8_to_bf16(unsigned w, unsigned mask, unsigned base) {
-  u32x4_t r;
-  r[0] = (w & mask) | base;
-  r[1] = (__builtin_amdgcn_alignbit(w, w, 4) & mask) | base;
-  r[2] = (__builtin_amdgcn_alignbit(w, w, 8) & mask) | base;
-  r[3] = (__builtin_amdgcn_alignbit(w, w, 12) & mask) | base;
-  return r;
-}
-
-// f(integral_constant<S>) for S = 0, 1, ... while f returns true
-template <int... S, typename F>
-LSA_DEVICE bool static_all(std::integer_sequence<int, S...>, F&& f) {
-  return (f(std::integral_constant<int, S>{}) && ...);
-}
 
 // byte offset of 16-B piece c16 (0..15) of row ``row`` in an A chunk of 256-B rows
 LSA_DEVICE int a_off(int row, int c16) { return row * 256 + ((c16 ^ (row & 15)) << 4); }
@@ -58,13 +34,10 @@ __global__ __launch_bounds__(NW * 64) void gemv_coop_int4_kernel(
     const bf16_raw* __restrict__ x, int ldx, const int* __restrict__ a_rows, const unsigned char* __restrict__ wq,
     const float* __restrict__ wscale, int M, int N, int K, int SK, float eps, EpiArgs ep, float* __restrict__ slab,
     unsigned* __restrict__ counters) {
-  constexpr int NTHR = NW * 64;
-  constexpr int MR = 16 * MB;
-  constexpr int TG = NW * TNW;           // 16-column tiles per workgroup
-  constexpr int ABUF = MR * 256;         // bytes per A chunk
-  constexpr int RS = 20;                 // reduction tile row stride (floats): 16 + 4 pad
-  constexpr int RED = TG * MR * RS * 4;  // fp32 reduction tile [TG][MR][RS]
-  constexpr int SMEM = 2 * ABUF > RED ? 2 * ABUF : RED;
+  using Geo = W4CoopGeo<MB, TNW, NW>;
+  constexpr int NTHR = Geo::NTHR, MR = Geo::MR, TG = Geo::TG, RS = Geo::RS;
+  constexpr int ABUF = MR * 256;  // bytes per A chunk
+  constexpr int SMEM = 2 * ABUF > Geo::RED ? 2 * ABUF : Geo::RED;
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   __shared__ __attribute__((aligned(16))) float s_rs[2][MR];  // row sums of the chunk in each A buffer
   __shared__ float s_ss[MR];
@@ -223,137 +196,27 @@ __global__ __launch_bounds__(NW * 64) void gemv_coop_int4_kernel(
     for (int i = 0; i < LPT; ++i) ss[i] = group_sum<16>(ss[i]);
   }
 
+  // the reduction tile, the split-K hand-off and the aligned epilogue: w4_coop_tail.h. The sums of
+  // squares are in the registers of each row's first staging thread
   float* red = reinterpret_cast<float*>(smem);  // [TG][MR][RS]
-  if (SK == 1) {
-#pragma unroll
-    for (int rb = 0; rb < MB; ++rb)
-#pragma unroll
-      for (int t = 0; t < TNW; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          red[((w * TNW + t) * MR + rb * 16 + kq * 4 + r) * RS + (lane & 15)] = acc[rb][t][r];
+  auto ss_rows = [&](auto put) {
     if (NORM && ac16 == 0) {
 #pragma unroll
-      for (int i = 0; i < LPT; ++i) s_ss[arow + i * RSTEP] = ss[i];
+      for (int i = 0; i < LPT; ++i) put(arow + i * RSTEP, ss[i]);
     }
-  } else {
-    // Split-K hand-off as in kernels/gemv_coop.hip: partials stored write-through (sc1, 16-B
-    // stores), every wave drains its stores, the workgroup barriers, one lane takes a relaxed
-    // agent-scope ticket; the workgroup that draws SK-1 reads all slabs with sc1 loads.
-    // Slab: [SK][N/16 tiles][MB][64 lanes][4] fp32 (fragment-native), then [SK][CG][MR] sums of squares.
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)slab, (short)0, 0x7fffffff, 0x00020000);
-    const int split_stride = (N >> 4) * MR * 16;  // floats
-#pragma unroll
-    for (int rb = 0; rb < MB; ++rb)
-#pragma unroll
-      for (int t = 0; t < TNW; ++t)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[rb][t]), pr,
-                                               ((((nt0 + t) * MB + rb) * 64 + lane) * 4) * 4, s * split_stride * 4,
-                                               16 /* sc1 */);
-    const int ss_base = SK * split_stride;  // floats
-    if (NORM && ac16 == 0) {
-#pragma unroll
-      for (int i = 0; i < LPT; ++i)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ss[i]), pr, ((s * CG + cg) * MR + arow + i * RSTEP) * 4,
-                                              ss_base * 4, 16);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&counters[cg], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(SK - 1);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // Last arriver: sum the SK slabs in fixed split order (deterministic). The group's region is
-    // one contiguous run of TG*MB*256 floats per split; E4 16-B loads x 4 splits in flight.
-    constexpr int E4 = TG * MB * 64 / NTHR;
-    const int gbase = cg * TG * MB * 256;  // floats
-    f32x4_t sum[E4];
-#pragma unroll
-    for (int j = 0; j < E4; ++j) sum[j] = fzero;
-    for (int q0 = 0; q0 < SK; q0 += 4) {
-      f32x4_t v[4][E4];
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const int q = q0 + qq < SK ? q0 + qq : 0;
-#pragma unroll
-        for (int j = 0; j < E4; ++j)
-          v[qq][j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                     pr, (gbase + (j * NTHR + tid) * 4) * 4, q * split_stride * 4, 16));
-      }
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq)
-        if (q0 + qq < SK)
-#pragma unroll
-          for (int j = 0; j < E4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sum[j][r] += v[qq][j][r];  // element by element: no packed FP32 adds
-    }
-#pragma unroll
-    for (int j = 0; j < E4; ++j) {
-      const int u = j * NTHR + tid;
-      const int tl = u / (MB * 64), rb = (u >> 6) % MB, ln = u & 63;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[(tl * MR + rb * 16 + (ln >> 4) * 4 + r) * RS + (ln & 15)] = sum[j][r];
-    }
-    if (NORM) {
-      for (int r = tid; r < MR; r += NTHR) {
-        float t2 = 0.f;
-        for (int q = 0; q < SK; ++q)
-          t2 += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pr, ((q * CG + cg) * MR + r) * 4, ss_base * 4, 16));
-        s_ss[r] = t2;
-      }
-    }
-    if (tid == 0) __hip_atomic_store(&counters[cg], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
+  };
+  if (!w4_coop_reduce<MB, TNW, NW, NORM, 4>(red, s_ss, &s_last, acc, slab, counters, cg, CG, s, SK, ss_rows)) return;
 
-  auto rstd = [&](int mm) -> float { return NORM ? rsqrtf(s_ss[mm] / (float)K + eps) : 1.f; };
   // 16-B stores (and 16-B residual / bias / cos / sin loads) need 16-B aligned rows; a caller
   // whose rows are not gets element stores
   const size_t al = (size_t)ep.out | (size_t)ep.resid | (size_t)ep.bias | (size_t)ep.k_cache | (size_t)ep.v_cache |
                     (size_t)ep.cos_t | (size_t)ep.sin_t | (size_t)(ep.ldo * 2) | (size_t)(ep.ldr * 2);
-  const bool vec = (al & 15) == 0;
-  if (vec) {
-    // rows RS = 20 floats apart: the 16 rows one ds_read_b128 lane group reads start 20 banks apart
-    auto load16 = [&](int t, int mm, float r, float* v) {
-      const float* rp = red + (t * MR + mm) * RS;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4_t x4 = *reinterpret_cast<const f32x4_t*>(rp + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * q + j] = x4[j] * r;
-      }
-    };
-    if (EPI == EPI_SWIGLU) {
-      // gate tile 2tp / up tile 2tp+1 -> 16 outputs per thread, two 16-B stores
-      for (int e = tid; e < (TG / 2) * MR; e += NTHR) {
-        const int tp = e / MR, mm = e % MR;
-        if (mm >= M) continue;
-        const float r = rstd(mm);
-        float gg[16], uu[16];
-        load16(2 * tp, mm, r, gg);
-        load16(2 * tp + 1, mm, r, uu);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) gg[j] = silu(gg[j]) * uu[j];
-        bf16_raw* o = ep.out + (size_t)mm * ep.ldo + (tlo / 2 + tp) * 16;
-        st16(o, pack8(gg));
-        st16(o + 8, pack8(gg + 8));
-      }
-    } else {
-      // one thread per finished 16-column tile row (epilogue.h epi_row16)
-      for (int e = tid; e < TG * MR; e += NTHR) {
-        const int t = e / MR, mm = e % MR;
-        if (mm >= M) continue;
-        float v[16];
-        load16(t, mm, rstd(mm), v);
-        epi_row16<EPI>(ep, mm, (tlo + t) * 16, v);
-      }
-    }
+  if ((al & 15) == 0) {
+    w4_coop_epilogue16<MB, TNW, NW, EPI, NORM, false>(red, s_ss, ep, M, K, eps, tlo, 0);
   } else {
     // gemv_int4.hip's element epilogue, for a C caller: ops/hip.py make_epi refuses unaligned rows, so
     // nothing in the Python package reaches this branch and no test runs it
+    auto rstd = [&](int mm) -> float { return w4_coop_rstd<NORM>(s_ss, mm, K, eps); };
     auto at = [&](int t, int mm, int n) -> float { return red[(t * MR + mm) * RS + n]; };
     if (EPI == EPI_SWIGLU) {
       for (int e = tid; e < (TG / 2) * MR * 16; e += NTHR) {
@@ -430,13 +293,8 @@ extern "C" int lsa_gemv_coop_int4(const void* x, int ldx, const int* a_rows, con
   const bf16_raw* xx = static_cast<const bf16_raw*>(x);
   const unsigned char* w = static_cast<const unsigned char*>(wq4);
   const bool nrm = norm != 0;
-#define LSA_E(E) launch_epi<E>(mb, tnw, nw, d, nrm, xx, ldx, a_rows, w, scales, M, N, K, sk, eps, *ep, slab, counters, stream)
-  switch (epi) {
-    case EPI_STORE: return LSA_E(EPI_STORE);
-    case EPI_RESID: return LSA_E(EPI_RESID);
-    case EPI_SWIGLU: return LSA_E(EPI_SWIGLU);
-    case EPI_QKV: return LSA_E(EPI_QKV);
-    default: return LSA_UNSUPPORTED;  // no arg-max epilogue: the lm_head stays bf16
-  }
-#undef LSA_E
+  return dispatch_epi(epi, [&](auto e) {
+    return launch_epi<decltype(e)::value>(mb, tnw, nw, d, nrm, xx, ldx, a_rows, w, scales, M, N, K, sk, eps, *ep, slab,
+                                          counters, stream);
+  });
 }

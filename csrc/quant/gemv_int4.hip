@@ -23,25 +23,9 @@
 //    projection. The VALU keeps to the nibble conversion.
 // Same register double-buffering / K split over waves / LDS reduction as gemv_fp8.hip; a wave's K
 // range is a whole number of groups (any group count: a chunk's tail groups are skipped).
-#include "../kernels/epilogue.h"
+#include "w4_common.h"  // int4x8_to_bf16 and its constants, dispatch_epi
 
 namespace {
-
-constexpr unsigned kNibMask = 0x00780078u;  // a nibble at mantissa bits 3..6 of both halves
-constexpr unsigned kBf16x16 = 0x41804180u;  // bf16 (16.0, 16.0)
-constexpr float kOffset = 24.0f;            // 16 (the bf16 base) + 8 (the nibble offset)
-
-// one packed dword (8 nibbles = one lane's share of a 32-k B fragment) -> 8 bf16 (q + 24).
-// ``mask`` / ``base`` arrive as registers (an SGPR and a VGPR the caller made opaque), so that
-// (w & mask) | base is ONE v_and_or_b32: with two literals the compiler has to emit v_and + v_or
-LSA_DEVICE u32x4_t int4x8_to_bf16(unsigned w, unsigned mask, unsigned base) {
-  u32x4_t r;
-  r[0] = (w & mask) | base;
-  r[1] = (__builtin_amdgcn_alignbit(w, w, 4) & mask) | base;
-  r[2] = (__builtin_amdgcn_alignbit(w, w, 8) & mask) | base;
-  r[3] = (__builtin_amdgcn_alignbit(w, w, 12) & mask) | base;
-  return r;
-}
 
 // UG = 16-B weight loads (= scale groups of 4 k-fragments) per pipeline chunk and tile
 template <int TN, int MB, int NW, int UG, int EPI, bool NORM>
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_int4_kernel(
   const int lane16 = lane * 16, lane4 = (lane & 15) * 4;
   unsigned mask = kNibMask, base = kBf16x16;
   asm volatile("" : "+s"(mask), "+v"(base));  // no instruction: hides the constants (int4x8_to_bf16)
-  const u32x4_t ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};  // bf16 1.0 x 8
+  const u32x4_t ones = {kBf16One, kBf16One, kBf16One, kBf16One};
   const f32x4_t fzero = {0.f, 0.f, 0.f, 0.f};
 
   auto load = [&](int g, u32x4_t (&b)[UG][TN], float (&sc)[UG][TN], u32x4_t (&a)[U][MB]) {
@@ -290,13 +274,9 @@ extern "C" int lsa_gemv_int4(const void* x, int ldx, const int* a_rows, const vo
   const bf16_raw* xx = static_cast<const bf16_raw*>(x);
   const unsigned char* w = static_cast<const unsigned char*>(wq4);
   const bool nrm = norm != 0;
-  switch (epi) {
-    case EPI_STORE: return launch_epi<EPI_STORE>(tn, nw, ug, nrm, xx, ldx, a_rows, w, scales, M, N, K, eps, *ep, stream);
-    case EPI_RESID: return launch_epi<EPI_RESID>(tn, nw, ug, nrm, xx, ldx, a_rows, w, scales, M, N, K, eps, *ep, stream);
-    case EPI_SWIGLU: return launch_epi<EPI_SWIGLU>(tn, nw, ug, nrm, xx, ldx, a_rows, w, scales, M, N, K, eps, *ep, stream);
-    case EPI_QKV: return launch_epi<EPI_QKV>(tn, nw, ug, nrm, xx, ldx, a_rows, w, scales, M, N, K, eps, *ep, stream);
-    default: return LSA_UNSUPPORTED;  // no arg-max epilogue: the lm_head stays bf16
-  }
+  return dispatch_epi(epi, [&](auto e) {
+    return launch_epi<decltype(e)::value>(tn, nw, ug, nrm, xx, ldx, a_rows, w, scales, M, N, K, eps, *ep, stream);
+  });
 }
 
 extern "C" int lsa_dequant_int4_packed(const void* wq4, const float* scales, void* wp, int N, int K,

@@ -22,45 +22,35 @@
 //    per K-step. The NW waves share it; the fused RMSNorm's sum of squares is taken from the
 //    bf16 values on the same pass, so rstd is that of the unquantised row.
 //  * K is split over SK workgroups in whole 512-k groups (the last may be short: K / 128 need not
-//    be a multiple of 4) with gemv_coop_int4.hip's wait-free hand-off: partial tiles go to a slab
-//    with write-through stores, an arrival counter per column group picks the last arriver, which
-//    sums the splits in fixed order, resets the counter and runs the epilogue.
+//    be a multiple of 4) with the wait-free hand-off of w4_common.h: partial tiles (and partial
+//    sums of squares) through a slab, an arrival counter per column group (w4_coop_tail.h,
+//    shared with gemv_coop_int4.hip).
 //  * A workgroup's last waves may own tiles past N / 16 (any tile count is served): they run on a
 //    clamped tile and their results are dropped.
-#include "../kernels/epilogue.h"
 #include "mx8_quant.h"
-
-#include <utility>
+#include "w4_coop_tail.h"
 
 namespace {
 
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
-template <int... S, typename F>
-LSA_DEVICE bool static_all(std::integer_sequence<int, S...>, F&& f) {
-  return (f(std::integral_constant<int, S>{}) && ...);
-}
-
 template <int MB, int TNW, int NW, int EPI, bool NORM>
 __global__ __launch_bounds__(NW * 64) void gemv_mx4_kernel(
     const bf16_raw* __restrict__ x, int ldx, const int* __restrict__ a_rows, const unsigned char* __restrict__ wq,
     const unsigned* __restrict__ wscale, int M, int N, int K, int SK, float eps, EpiArgs ep, float* __restrict__ slab,
     unsigned* __restrict__ counters) {
-  constexpr int NTHR = NW * 64;
-  constexpr int MR = 16 * MB;
-  constexpr int TG = NW * TNW;            // 16-column tiles per workgroup
+  using Geo = W4CoopGeo<MB, TNW, NW>;
+  constexpr int MR = Geo::MR, TG = Geo::TG;
   constexpr int ACODE = MB * 2 * 1024;    // e4m3 codes of one K-step: [MB][2 halves][64 lanes][16 B]
   constexpr int ABUF = ACODE + MB * 256;  // + the exponent dwords [MB][64 lanes]
-  constexpr int RS = 20;                  // reduction tile row stride (floats): 16 + 4 pad
-  constexpr int RED = TG * MR * RS * 4;   // fp32 reduction tile [TG][MR][RS]
-  constexpr int SMEM = 2 * ABUF > RED ? 2 * ABUF : RED;
+  constexpr int SMEM = 2 * ABUF > Geo::RED ? 2 * ABUF : Geo::RED;
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   __shared__ float s_ssp[4][MR];  // sums of squares by 32-block of the K-step
   __shared__ float s_ss[MR];
   __shared__ int s_last;
 
-  const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int KS = K >> 7, NG = (KS + 3) >> 2, NT = N >> 4;  // K-steps, scale groups, tiles
   const int CG = (NT + TG - 1) / TG;                        // column groups
@@ -225,118 +215,15 @@ __global__ __launch_bounds__(NW * 64) void gemv_mx4_kernel(
     }
   }
 
+  // the reduction tile, the split-K hand-off and the epilogue: w4_coop_tail.h. A row's sum of
+  // squares is the sum of its four 32-block partials, once every wave has written s_ssp
   float* red = reinterpret_cast<float*>(smem);  // [TG][MR][RS]
-  if (SK == 1) {
-#pragma unroll
-    for (int rb = 0; rb < MB; ++rb)
-#pragma unroll
-      for (int t = 0; t < TNW; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          red[((w * TNW + t) * MR + rb * 16 + kq * 4 + r) * RS + (lane & 15)] = acc[rb][t][r];
+  auto ss_rows = [&](auto put) {
     __syncthreads();
-    if (NORM && tid < MR) s_ss[tid] = (s_ssp[0][tid] + s_ssp[1][tid]) + (s_ssp[2][tid] + s_ssp[3][tid]);
-  } else {
-    // Split-K hand-off as in gemv_coop_int4.hip: partials stored write-through (sc1, 16-B stores),
-    // every wave drains its stores, the workgroup barriers, one lane takes a relaxed agent-scope
-    // ticket; the workgroup that draws SK-1 reads all slabs with sc1 loads.
-    // Slab: [SK][CG * TG tiles][MB][64 lanes][4] fp32 (fragment-native), then [SK][CG][MR] sums of squares.
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)slab, (short)0, 0x7fffffff, 0x00020000);
-    const int split_stride = CG * TG * MR * 16;  // floats
-#pragma unroll
-    for (int rb = 0; rb < MB; ++rb)
-#pragma unroll
-      for (int t = 0; t < TNW; ++t)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[rb][t]), pr,
-                                               ((((nt0 + t) * MB + rb) * 64 + lane) * 4) * 4, s * split_stride * 4,
-                                               16 /* sc1 */);
-    const int ss_base = SK * split_stride;  // floats
-    __syncthreads();                        // s_ssp is complete
-    if (NORM && tid < MR) {
-      const float t = (s_ssp[0][tid] + s_ssp[1][tid]) + (s_ssp[2][tid] + s_ssp[3][tid]);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(t), pr, ((s * CG + cg) * MR + tid) * 4, ss_base * 4, 16);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&counters[cg], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(SK - 1);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // Last arriver: sum the SK slabs in fixed split order (deterministic). The group's region is
-    // one contiguous run of TG*MB*256 floats per split.
-    constexpr int E4 = TG * MB * 64 / NTHR;
-    const int gbase = cg * TG * MB * 256;  // floats
-    f32x4_t sum[E4];
-#pragma unroll
-    for (int j = 0; j < E4; ++j) sum[j] = fzero;
-    for (int q = 0; q < SK; ++q) {
-      f32x4_t v[E4];
-#pragma unroll
-      for (int j = 0; j < E4; ++j)
-        v[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(pr, (gbase + (j * NTHR + tid) * 4) * 4,
-                                                                                  q * split_stride * 4, 16));
-#pragma unroll
-      for (int j = 0; j < E4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sum[j][r] += v[j][r];  // element by element: no packed FP32 adds
-    }
-#pragma unroll
-    for (int j = 0; j < E4; ++j) {
-      const int u = j * NTHR + tid;
-      const int tl = u / (MB * 64), rb = (u >> 6) % MB, ln = u & 63;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[(tl * MR + rb * 16 + (ln >> 4) * 4 + r) * RS + (ln & 15)] = sum[j][r];
-    }
-    if (NORM) {
-      for (int r = tid; r < MR; r += NTHR) {
-        float t2 = 0.f;
-        for (int q = 0; q < SK; ++q)
-          t2 += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pr, ((q * CG + cg) * MR + r) * 4, ss_base * 4, 16));
-        s_ss[r] = t2;
-      }
-    }
-    if (tid == 0) __hip_atomic_store(&counters[cg], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-
-  auto rstd = [&](int mm) -> float { return NORM ? rsqrtf(s_ss[mm] / (float)K + eps) : 1.f; };
-  // rows RS = 20 floats apart: the 16 rows one ds_read_b128 lane group reads start 20 banks apart
-  auto load16 = [&](int t, int mm, float r, float* v) {
-    const float* rp = red + (t * MR + mm) * RS;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4_t x4 = *reinterpret_cast<const f32x4_t*>(rp + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[4 * q + j] = x4[j] * r;
-    }
+    if (NORM && tid < MR) put(tid, (s_ssp[0][tid] + s_ssp[1][tid]) + (s_ssp[2][tid] + s_ssp[3][tid]));
   };
-  if (EPI == EPI_SWIGLU) {
-    // gate tile 2tp / up tile 2tp+1 -> 16 outputs per thread, two 16-B stores (host: N / 16 and TG even)
-    for (int e = tid; e < (TG / 2) * MR; e += NTHR) {
-      const int tp = e / MR, mm = e % MR;
-      if (mm >= M || tlo + 2 * tp >= NT) continue;
-      const float r = rstd(mm);
-      float gg[16], uu[16];
-      load16(2 * tp, mm, r, gg);
-      load16(2 * tp + 1, mm, r, uu);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) gg[j] = silu(gg[j]) * uu[j];
-      bf16_raw* o = ep.out + (size_t)mm * ep.ldo + (tlo / 2 + tp) * 16;
-      st16(o, pack8(gg));
-      st16(o + 8, pack8(gg + 8));
-    }
-  } else {
-    // one thread per finished 16-column tile row (epilogue.h epi_row16)
-    for (int e = tid; e < TG * MR; e += NTHR) {
-      const int t = e / MR, mm = e % MR;
-      if (mm >= M || tlo + t >= NT) continue;
-      float v[16];
-      load16(t, mm, rstd(mm), v);
-      epi_row16<EPI>(ep, mm, (tlo + t) * 16, v);
-    }
-  }
+  if (!w4_coop_reduce<MB, TNW, NW, NORM, 1>(red, s_ss, &s_last, acc, slab, counters, cg, CG, s, SK, ss_rows)) return;
+  w4_coop_epilogue16<MB, TNW, NW, EPI, NORM, true>(red, s_ss, ep, M, K, eps, tlo, NT);
 }
 
 template <int MB, int TNW, int NW, int EPI>
@@ -424,15 +311,10 @@ extern "C" int lsa_gemv_mx4(const void* x, int ldx, const int* a_rows, const voi
   const unsigned char* w = static_cast<const unsigned char*>(wq);
   const unsigned* sc = static_cast<const unsigned*>(scales);
   const bool nrm = norm != 0;
-#define LSA_E(E) launch_epi<E>(mb, tnw, nw, nrm, xx, ldx, a_rows, w, sc, M, N, K, sk, eps, *ep, slab, counters, stream)
-  switch (epi) {
-    case EPI_STORE: return LSA_E(EPI_STORE);
-    case EPI_RESID: return LSA_E(EPI_RESID);
-    case EPI_SWIGLU: return LSA_E(EPI_SWIGLU);
-    case EPI_QKV: return LSA_E(EPI_QKV);
-    default: return LSA_UNSUPPORTED;  // no arg-max epilogue: the lm_head stays bf16
-  }
-#undef LSA_E
+  return dispatch_epi(epi, [&](auto e) {
+    return launch_epi<decltype(e)::value>(mb, tnw, nw, nrm, xx, ldx, a_rows, w, sc, M, N, K, sk, eps, *ep, slab,
+                                          counters, stream);
+  });
 }
 
 extern "C" int lsa_dequant_mx4_packed(const void* wq, const void* scales, void* wp, int N, int K, hipStream_t stream) {
